@@ -19,10 +19,18 @@ ONE kernel:
 per channel-sample -- over its measured duration: `frac` is a physical fraction of the HBM
 peak (<= 1); the 48 B per sample the unfused chain would move (FIR 16 +
 sosfiltfilt 32) appear only as `unfused_equivalent_*`.  `value` is W warm-up steps, then K
-timed steps, as the driver's contract says; `steady_state` (not `value`) is the same K steps
-timed once more 40 steps further into the stream: the first ~30 launches after the GPU was idle
-run slower while its clock / power controller settles (benchmarks/ramp_probe.py), which is what
-K = 20 behind W = 5 times.
+timed steps (`--warmup W --steps K`); with `--full`, `steady_state` (not `value`) is the
+same K steps timed once more 40 steps further into the stream: the first ~30 launches after the
+GPU was idle run slower while its clock / power controller settles (benchmarks/ramp_probe.py),
+which is what K = 20 behind W = 5 times.
+
+A plain run does only what the headline line needs: set up, warm up, time the K steps, write
+the outputs (`--dump-outputs DIR`) and print the line.  `--full` adds everything else the line
+reports: `cpu_baseline`, `steady_state` and, at N > 1, the strong-scaling leg (`strong`).
+`--dump-outputs DIR` writes what the timed path computed in its last timed step as
+DIR/<name>.npy (float64; a fixed, seeded sample of a large output, 64 MB at most in all); the
+inputs are synthesised from fixed seeds, so two builds run with the same arguments can be
+compared output for output.
 
 Inputs are synthesised on the device before the timed region (a ring of
 resident chunks keyed by (seed, channel, sample)); outputs land in a resident
@@ -47,7 +55,7 @@ ranks are already there and the script runs as one of them.  `--dry` runs the
 launcher, the barriers and the collectives on CPU (gloo) without any kernel.
 
 Prints ONE JSON line (see README / the driver contract) with `roofline` for
-the dominant kernel and, at N=1 on rank 0, `cpu_baseline` (the CPU oracle).
+the dominant kernel and, with `--full` at N=1 on rank 0, `cpu_baseline` (the CPU oracle).
 """
 
 import argparse
@@ -352,6 +360,49 @@ def roofline_of(kernels, samples_per_step):
     return out
 
 
+# ------------------------------------------------------------- --dump-outputs
+DUMP_WHOLE = 8 << 20         # bytes: an output up to this size is written whole
+DUMP_ROWS = 32 << 20         # bytes of whole rows (first axis) kept of a larger output
+DUMP_POINTS = 1 << 20        # single elements kept of a larger output, spread over all of it
+DUMP_LIMIT = 64_000_000      # bytes written in all
+DUMP_SEED = 20_240_517
+
+
+def dump_outputs(args, R, arrays):
+    """--dump-outputs: writes the arrays the timed path's caller received in its last timed step
+    as DIR/<name>.npy (rank 0's; complex as (..., 2) real pairs).  An array of up to DUMP_WHOLE
+    bytes is written whole; a larger one as a fixed, seeded sample, the same positions on every
+    run: whole rows of its first axis (<name>_rows.npy, their indices sorted) and DUMP_POINTS
+    elements of the flattened array (<name>_points.npy, at sorted positions)."""
+    if not args.dump_outputs or R.rank != 0:
+        return
+    torch = R.torch
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    files = {}
+    for name, t in arrays.items():
+        t = torch.as_tensor(t)
+        t = torch.view_as_real(t) if t.is_complex() else t
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        nbytes = t.numel() * t.element_size()
+        if nbytes <= DUMP_WHOLE:
+            files[name] = t
+            continue
+        row_bytes = nbytes // t.shape[0]
+        nrows = min(t.shape[0], DUMP_ROWS // row_bytes)
+        if nrows:
+            rows = np.sort(rng.choice(t.shape[0], nrows, replace=False))
+            files[name + "_rows"] = t[torch.as_tensor(rows, device=t.device)]
+        points = np.sort(rng.integers(0, t.numel(), DUMP_POINTS))
+        files[name + "_points"] = t.reshape(-1)[torch.as_tensor(points, device=t.device)]
+    files = {k: v.cpu().numpy() for k, v in files.items()}
+    total = sum(v.nbytes for v in files.values())
+    assert total <= DUMP_LIMIT, (total, {k: v.shape for k, v in files.items()})
+    for k, v in files.items():
+        np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
+
+
 # ------------------------------------------------------------ workload: chain
 def run_chain(args, R, h, sos):
     torch = R.torch
@@ -368,7 +419,7 @@ def run_chain(args, R, h, sos):
         elapsed = R.max_over_ranks(time.perf_counter() - t0)
         R.barrier()
         extra = {"channel_blocks": blocks.tolist()}
-        if R.world > 1 and args.scaling == "weak":
+        if args.full and R.world > 1 and args.scaling == "weak":
             # the strong leg's partition and gather (strong_leg below), without kernels
             from openseize_amd import sharding
             from openseize_amd.core import numerical as nm
@@ -467,12 +518,15 @@ def run_chain(args, R, h, sos):
     _lib.check(lib.osz_profile_enable(0))
     elapsed = R.max_over_ranks(elapsed)
     R.barrier()
-    # The same K steps once more, further into the stream (NOT `value`): the first ~30 launches
-    # after the GPU was idle run up to 40 % slower while its clock / power controller settles
-    # (benchmarks/ramp_probe.py: the same on the same buffers after a 2 s pause), so K = 20
+    # the output chunk the last timed step finished (zero-phase kernel: the one two chunks behind
+    # its input, sealed by that step; the older sequences: y_out)
+    dump_outputs(args, R, {"chain_output": fwd[(k - 3) % nf] if zp else y_out})
+    # --full: the same K steps once more, further into the stream (NOT `value`): the first ~30
+    # launches after the GPU was idle run up to 40 % slower while its clock / power controller
+    # settles (benchmarks/ramp_probe.py: the same on the same buffers after a 2 s pause), so K = 20
     # steps behind W = 5 time that transient; a stream of hours runs at the rate below.
     steady = None
-    if zp and not args.no_steady:
+    if zp and args.full and not args.no_steady:
         for _ in range(max(launches, 40 - launches - warm_launches)):
             step(k)
             k += 1
@@ -513,8 +567,9 @@ def run_chain(args, R, h, sos):
         fir.close()
         iir.close()
         extra["full_stream"] = full_stream_leg(R, ring, h, sos)
-    # (OSZ_BENCH_STRONG=1: the leg also at one rank -- how its code is exercised on a one-GPU box)
-    if zp and (R.world > 1 or os.environ.get("OSZ_BENCH_STRONG") == "1") and args.scaling == "weak":
+    # --full (OSZ_BENCH_STRONG=1: the leg also at one rank -- how its code is exercised on one GPU)
+    if (zp and args.full and (R.world > 1 or os.environ.get("OSZ_BENCH_STRONG") == "1")
+            and args.scaling == "weak"):
         del fwd, y_out, fir_out, ring
         fir.close()
         iir.close()
@@ -710,6 +765,7 @@ def run_welch(args, R):
     _lib.check(lib.osz_profile_enable(0))
     elapsed = R.max_over_ranks(elapsed)
     R.barrier()
+    dump_outputs(args, R, {"psd": mean, "psd_segments": [cnt]})
     spec.close()
     kernels = kernel_table(lib, C * CHUNK)
     # ---- untimed check: time split over the ranks == single-rank PSD
@@ -770,6 +826,7 @@ def run_fir(args, R, h):
     _lib.check(lib.osz_profile_enable(0))
     elapsed = R.max_over_ranks(elapsed)
     R.barrier()
+    dump_outputs(args, R, {"fir_output": out})
     bits, fsum = dev.checksum(out)
     fir.close()
     kernels = kernel_table(lib, C * CHUNK)
@@ -822,10 +879,11 @@ def run_stft(args, R):
     poly = dev.PolyStream(hk, 1, 5, C)
     spec = dev.SpecStream(NFFT, NFFT, NFFT // 2, w, scale, "constant", _lib.SPEC_DFT_SEGMENTS, C)
     nseg = 0
+    last = {}
 
     def step(k):
         y = poly.push(ring[k % 3], final=False)
-        seg = spec.push(y)
+        seg = last["stft_segments"] = spec.push(y)
         return 0 if seg is None else seg.shape[0]
 
     for k in range(max(args.warmup, 1)):
@@ -841,6 +899,7 @@ def run_stft(args, R):
     _lib.check(lib.osz_profile_enable(0))
     elapsed = R.max_over_ranks(elapsed)
     R.barrier()
+    dump_outputs(args, R, last)
     poly.close()
     spec.close()
     kernels = kernel_table(lib, C * CHUNK)
@@ -874,12 +933,18 @@ def main():
     ap.add_argument("--reduce", choices=("torch", "abi"), default="torch",
                     help="welch: all-reduce through torch.distributed (RCCL) or through "
                          "osz_welch_reduce of the C ABI")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the cpu_baseline leg, the later timing of the same steps "
+                         "(steady_state) and, at N > 1, the strong-scaling leg")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy "
+                         "(float64, a fixed seeded sample of a large output, at most 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--zp-tol", type=float, default=0.0,
                     help="A/B: where the chain kernel cuts its bursts (0: the library's default, 1e-15; "
                          "rounds 3-4 ran 1e-12 on zero-mean data)")
     ap.add_argument("--no-steady", action="store_true",
-                    help="skip the second, later timing of the same steps (steady_state)")
+                    help="with --full: skip the second, later timing of the same steps (steady_state)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="chain: weak = 256 channels per rank; strong = the metric's 256 channels "
                          "split over the ranks (32 per GPU at 8 ranks)")
@@ -905,6 +970,8 @@ def main():
     ap.add_argument("--dry", action="store_true",
                     help="launcher, barriers and collectives on CPU (gloo), no kernels")
     args = ap.parse_args()
+    if args.dump_outputs and args.dry:
+        ap.error("--dump-outputs needs the kernels: a --dry run computes no outputs")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch(args))
 
@@ -913,7 +980,8 @@ def main():
     sos = sps.butter(6, [0.05, 0.3], "bandpass", output="sos")
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     cpu = None
-    if int(os.environ.get("RANK", "0")) == 0 and world_env == 1 and not (args.no_cpu or args.dry):
+    if (args.full and int(os.environ.get("RANK", "0")) == 0 and world_env == 1
+            and not (args.no_cpu or args.dry)):
         cpu = cpu_baseline(args.workload, h, sos)       # before any GPU initialisation
     R = Ranks(args.dry)
     if args.workload == "welch":
