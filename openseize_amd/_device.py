@@ -40,6 +40,12 @@ def stack(arrs, axis):
     return np.stack(arrs, axis=axis)
 
 
+def copy(a):
+    """A copy of an ndarray or tensor in memory of its own (a tensor on its device, queued on
+    the current stream)."""
+    return a.clone() if is_tensor(a) else np.array(a, copy=True)
+
+
 def size(a):
     return a.numel() if is_tensor(a) else a.size
 

@@ -25,7 +25,7 @@ import scipy.signal as sps
 
 from openseize_amd import _device as dev
 from openseize_amd import _lib
-from openseize_amd.core import protools
+from openseize_amd.core import protools, sources
 from openseize_amd.core.arraytools import normalize_axis, slice_along_axis
 from openseize_amd.core.producer import ArrayProducer, producer
 
@@ -79,7 +79,9 @@ def _oa_cuts(wlen, mode):
 def _joined_resident(source, layout, gmax):
     """The chunks of ``source`` as 2-D arrays, those of a resident stream that lie one behind the
     other in memory joined up to ``gmax`` at a time (``_row_joined``): yields (2-D chunk, came from
-    the host, lengths of the produced chunks it holds).  Empty chunks are dropped."""
+    the host, lengths of the produced chunks it holds).  Empty chunks are dropped.  With ``gmax`` 1 every
+    chunk is handed on before the next one is pulled: what a source whose chunks may be rewritten
+    (``sources.stays_put``) needs."""
     held, sizes = None, []
     for arr in source:
         x2d, from_host = layout.to2d(arr)
@@ -180,23 +182,27 @@ class _ProbeWatch:
 
 class _Tee:
     """A producer as ``_oaconvolve_stream`` sees it (shape, chunksize, iteration) that remembers the
-    chunks it hands on: ``seen`` gets (first sample, samples, chunk) -- references, no copies."""
+    chunks it hands on: ``seen`` gets (first sample, samples, chunk) -- references, no copies, for a
+    source whose chunks stay put (``sources.stays_put``), copies for any other."""
 
     def __init__(self, pro, axis, seen):
         self.pro, self.axis, self.seen = pro, axis, seen
+        self.relays = pro
         self.shape = pro.shape
         self.chunksize = int(getattr(pro, "chunksize", 1 << 20))
 
     def __iter__(self):
         at = 0
+        keep = (lambda c: c) if sources.stays_put(self.pro) else dev.copy
         for chunk in self.pro:
             n = chunk.shape[self.axis]
             if n:
-                self.seen.append((at, n, chunk))
+                self.seen.append((at, n, keep(chunk)))
             at += n
             yield chunk
 
 
+@sources.fresh
 @dev.chain_aware
 def oaconvolve(pro, window, axis, mode, nfft_factor=32):
     """Streaming overlap-add convolution of a producer with a 1-D window
@@ -204,7 +210,7 @@ def oaconvolve(pro, window, axis, mode, nfft_factor=32):
     and around it the REACH of non-finite input samples as the reference has it.
 
     The reference transforms segments of ``step = nfft - wlen + 1`` input samples (nfft =
-    8 * 2^ceil(log2 wlen) * 32, :202-217); a non-finite sample makes the whole output of ITS
+    8 * 2^ceil(log2 wlen) * nfft_factor, :202-217); a non-finite sample makes the whole output of ITS
     segment non-finite -- 'full' samples [k step, (k + 1) step + wlen - 1) -- and nothing else
     (:258-283).  The kernels here transform blocks of a few thousand samples, so their own
     non-finite runs are shorter and start elsewhere.  The pieces are therefore held back until
@@ -216,20 +222,20 @@ def oaconvolve(pro, window, axis, mode, nfft_factor=32):
     over the piece.  ``OSZ_FIR_REACH=0``: the kernels' own reach (rounds 1-4).
     """
     if os.environ.get("OSZ_FIR_REACH", "1") == "0":
-        yield from _oaconvolve_stream(pro, window, axis, mode)
+        yield from _oaconvolve_stream(pro, window, axis, mode, nfft_factor)
         return
     import torch
     taps = np.asarray(window, dtype=np.float64)
     nsamples = pro.shape[axis]
     if taps.ndim != 1 or nsamples < len(taps):
-        yield from _oaconvolve_stream(pro, window, axis, mode)      # (raises, in its own words)
+        yield from _oaconvolve_stream(pro, window, axis, mode, nfft_factor)      # (raises, in its own words)
         return
     wlen = len(taps)
     lcut, _ = _oa_cuts(wlen, mode)
-    step = _oa_reference_step(nsamples, wlen)
+    step = _oa_reference_step(nsamples, wlen, nfft_factor)
     layout = dev.Layout(pro.shape, axis)
     seen = deque()
-    inner = _oaconvolve_stream(_Tee(pro, axis, seen), window, axis, mode, probed=True)
+    inner = _oaconvolve_stream(_Tee(pro, axis, seen), window, axis, mode, nfft_factor, probed=True)
     pending = deque()                 # [piece, its first sample ('full' numbering), samples, probe]
     produced = lcut                   # 'full' sample behind the last piece produced
     flagged_to = 0                    # 'full' sample behind the last piece whose probe tripped
@@ -381,6 +387,7 @@ def _oaconvolve_stream(pro, window, axis, mode, nfft_factor=32, probed=False):
     cur, fill = None, 0                      # open output buffer and its filled columns
     import torch
 
+    stays = sources.stays_put(pro)
     chunks = iter(pro)
     first = next(chunks, None)
     if first is not None and not dev.is_tensor(first):
@@ -411,8 +418,9 @@ def _oaconvolve_stream(pro, window, axis, mode, nfft_factor=32, probed=False):
     # Few channels or short chunks: chunks of a resident source that lie one behind the other in
     # memory (the views an ArrayProducer cuts from one tensor) are pushed several at a time -- as
     # many as make 2^28 channel-samples, as the zero-phase chain does (_zp_group) -- and handed on
-    # chunk by chunk: `cuts` are the lengths the open buffer is handed on in.
-    gmax = _zp_group(layout.nch, chunk_len)
+    # chunk by chunk: `cuts` are the lengths the open buffer is handed on in.  (Only for a source
+    # whose chunks stay put: any other one's chunk is pushed before the next one is pulled.)
+    gmax = _zp_group(layout.nch, chunk_len) if stays else 1
     cuts = []
 
     def emit(buf, cols):
@@ -501,6 +509,7 @@ def _zi_to_2d(zi, nsec, layout):
     return np.ascontiguousarray(zi.reshape(nsec, layout.nch, 2))
 
 
+@sources.fresh
 @dev.chain_aware
 def sosfilt(pro, sos, axis, zi=None):
     """Forward cascaded-biquad filter with the state carried from chunk to
@@ -530,8 +539,9 @@ def sosfilt(pro, sos, axis, zi=None):
                 _chain_first(first, chunks),
                 lambda x2d: stream.forward(x2d) if x2d.shape[1] else None)
             return
-        # (adjacent views of a resident stream go through the kernel several at a time, _zp_group)
-        gmax = _zp_group(layout.nch, int(getattr(pro, "chunksize", 1 << 20)))
+        # (adjacent views of a resident stream whose chunks stay put go through the kernel several
+        # at a time, _zp_group)
+        gmax = _zp_group(layout.nch, int(getattr(pro, "chunksize", 1 << 20))) if sources.stays_put(pro) else 1
         for x2d, host, sizes in _joined_resident(_chain_first(first, chunks), layout, gmax):
             y = stream.forward(x2d)
             if len(sizes) == 1:
@@ -546,7 +556,7 @@ def sosfilt(pro, sos, axis, zi=None):
 
 
 def _fir_feeding(pro, axis):
-    """(source producer, taps) when ``pro`` is what ``FIR.__call__`` /
+    """(source producer, taps, nfft_factor) when ``pro`` is what ``FIR.__call__`` /
     ``producer(partial(oaconvolve, ...), ...)`` builds: a generating producer over
     ``oaconvolve`` in mode 'same' along the same axis with the source's
     chunksize; None otherwise."""
@@ -565,6 +575,7 @@ def _fir_feeding(pro, axis):
         bound = inspect.signature(oaconvolve).bind(*gen.args, **{**(gen.keywords or {}), **pro.kwargs})
     except TypeError:
         return None
+    bound.apply_defaults()
     source, taps = bound.arguments["pro"], bound.arguments["window"]
     fir_axis, mode = bound.arguments["axis"], bound.arguments["mode"]
     if not isinstance(source, Producer) or mode != "same":
@@ -586,10 +597,11 @@ def _fir_feeding(pro, axis):
         return None
     if int(source.chunksize) != int(pro.chunksize):
         return None
-    return source, taps
+    # (the reference's segment length: where the reach of a non-finite sample starts)
+    return source, taps, bound.arguments["nfft_factor"]
 
 
-def _sosfilt_after_fir(pro, source, taps, sos, zi):
+def _sosfilt_after_fir(pro, source, taps, nfft_factor, sos, zi):
     """``sosfilt(oaconvolve(source, taps, 'same'))``, chunk for chunk what the two generators
     yield one after the other (reference core/numerical.py:158-298 feeding :301-335), on
     ``osz_chain_forward``: FIR and forward cascade of an input chunk in one launch, the FIR's
@@ -615,6 +627,7 @@ def _sosfilt_after_fir(pro, source, taps, sos, zi):
     last = total - (nchunks - 1) * cs
     if nchunks < 3 or cs < 65536 or total < wlen or last < max(lcut, 1):
         return None
+    stays = sources.stays_put(source)
     chunks = dev.pull_resident(source, source)         # a source of this library hands CUDA tensors
     first = next(chunks, None)
     if first is None or first.shape[axis] != cs or (dev.is_tensor(first) and not first.is_cuda):
@@ -662,7 +675,7 @@ def _sosfilt_after_fir(pro, source, taps, sos, zi):
             # reference's segments laid over its output, the cascade behind that (which loses the
             # channel by itself).  OSZ_CHAIN_REACH=0: the kernels' own reach.
             reach = os.environ.get("OSZ_CHAIN_REACH", "1") != "0"
-            step = _oa_reference_step(total, wlen)
+            step = _oa_reference_step(total, wlen, nfft_factor)
             pend, kept = deque(), deque()              # [j, piece, first 'full' sample, probe]; [k, chunk, states before it]
             slow = {"on": False, "out": deque(), "queue": deque(), "seen": 0, "parts": [], "have": 0,
                     "piece": 0, "skip": 0, "drop": 0, "bad": None}
@@ -776,10 +789,11 @@ def _sosfilt_after_fir(pro, source, taps, sos, zi):
                     return release(False)
                 if not reach:
                     return fused(x2d)
-                # (a host-fed chunk sits in a staging buffer that is written again: a copy is kept.  The
+                # (a host-fed chunk sits in a staging buffer that is written again, and a source whose
+                # chunks do not stay put may write its chunk again: a copy is kept.  The
                 # handles' states before every fourth push: reading them makes the forward link settle its
                 # carry into them -- five small launches -- and the slow way can start a few chunks early)
-                kept.append([k, x2d if resident else x2d.clone(),
+                kept.append([k, x2d if resident and stays else x2d.clone(),
                              (fir.snapshot(), iir.snapshot()) if k % 4 == 0 else None])
                 y = fused(x2d)
                 if y is not None:
@@ -835,7 +849,7 @@ def _sosfilt_after_fir(pro, source, taps, sos, zi):
     return run()
 
 
-def _sosfiltfilt_after_fir(pro, source, taps, sos):
+def _sosfiltfilt_after_fir(pro, source, taps, nfft_factor, sos):
     """``sosfiltfilt(oaconvolve(source, taps, 'same'))`` for a device-resident
     source, chunk for chunk what the two generators yield one after the other
     (reference core/numerical.py:158-298 feeding :338-411), on the steady-state
@@ -897,9 +911,10 @@ def _sosfiltfilt_after_fir(pro, source, taps, sos):
             if one_kernel:
                 # (the reference FIR's NaN reach, segment by segment; OSZ_ZP_REACH=0: the kernels' own,
                 # from the sample itself)
-                reach = 0 if os.environ.get("OSZ_ZP_REACH") == "0" else _oa_reference_step(total, wlen)
+                reach = 0 if os.environ.get("OSZ_ZP_REACH") == "0" else _oa_reference_step(total, wlen, nfft_factor)
                 yield from _zero_phase_stream(fir, iir, layout, pipe, flying, first, chunks, taps, cs, total,
-                                              lcut, rcut, lag, device, ref_step=reach)
+                                              lcut, rcut, lag, device, ref_step=reach,
+                                              stays=sources.stays_put(source))
                 return
 
             def feed(arr):
@@ -1044,21 +1059,21 @@ def _row_joined(a, b):
     return a.as_strided((a.shape[0], n), a.stride(), a.storage_offset())
 
 
-def _oa_reference_step(nsamples, wlen):
+def _oa_reference_step(nsamples, wlen, nfft_factor=32):
     """Input samples per FFT segment of the reference's overlap-add (core/numerical.py:202-217):
-    nfft = 8 * 2^ceil(log2 wlen) * 32 unless a segment of that size is longer than the data, then
+    nfft = 8 * 2^ceil(log2 wlen) * nfft_factor unless a segment of that size is longer than the data, then
     min(8 * 2^ceil(log2 wlen), N); step = nfft - wlen + 1.  A non-finite input sample makes its whole
     segment's output non-finite there (:258-283): the NaN reach of a chain behind the FIR counts from
     the segment's start."""
     base = int(8 * 2 ** math.ceil(math.log2(wlen)))
-    nfft = base * 32
+    nfft = base * int(nfft_factor)
     if nfft - wlen + 1 > nsamples:
         nfft = min(base, int(nsamples))
     return max(nfft - wlen + 1, 1)
 
 
 def _zero_phase_stream(fir, iir, layout, pipe, flying, first, chunks, taps, cs, total, lcut, rcut, lag, device,
-                       what="sosfiltfilt after oaconvolve", ref_step=0):
+                       what="sosfiltfilt after oaconvolve", ref_step=0, stays=True):
     """The body of ``_sosfiltfilt_after_fir`` on the zero-phase kernel (C ABI: osz_chain_zp_*,
     csrc/chain_zp.hip): FIR, forward and backward cascade of an input chunk in ONE launch.
 
@@ -1087,7 +1102,11 @@ def _zero_phase_stream(fir, iir, layout, pipe, flying, first, chunks, taps, cs, 
     reach spans chunks, so that the chunks the reference loses are still here to be lost.  In
     the stream's last two chunks (separate kernels, whose FIR makes its own 4096-point blocks
     non-finite) the forward stream is recomputed from a cleaned copy and poisoned by the
-    reference's rule when a channel first goes bad there."""
+    reference's rule when a channel first goes bad there.
+
+    ``stays`` False: the source's chunks may be written again once the next one is pulled
+    (``sources.stays_put``): every chunk is launched on its own before the next is pulled, and
+    the one chunk read again at the end is copied."""
     import torch
     C = layout.nch
     wlen = len(taps)
@@ -1134,8 +1153,10 @@ def _zero_phase_stream(fir, iir, layout, pipe, flying, first, chunks, taps, cs, 
     # that lie one behind the other in memory -- the views an ArrayProducer cuts from one tensor
     # -- therefore go through the kernel several at a time: `gmax` of them make one step of as
     # many channel-samples as a 256-channel chunk of 2^20; the results are handed on chunk by
-    # chunk as before (views of the step's output buffer).
-    gmax = _zp_group(C, cs) if pipe is None else 1
+    # chunk as before (views of the step's output buffer).  (A host-fed chunk has been uploaded to
+    # memory of its own; a resident one whose source may write it again is launched before the
+    # next one is pulled.)
+    gmax = _zp_group(C, cs) if pipe is None and stays else 1
     group, emitted = [], 0                                    # [(k, 2-D view)]; chunks handed on so far
 
     def run_group():
@@ -1164,10 +1185,12 @@ def _zero_phase_stream(fir, iir, layout, pipe, flying, first, chunks, taps, cs, 
             raise RuntimeError(f"{what}: an inner chunk of the source is not chunksize = {cs} long")
         if k == nchunks - 2:
             break
-        if group and (len(group) >= gmax or _row_joined(group[-1][1], x2d) is None):
+        if group and _row_joined(group[-1][1], x2d) is None:
             yield from run_group()
         group.append((k, x2d))
         k += 1
+        if len(group) >= gmax:
+            yield from run_group()
     if group:
         yield from run_group()
     if k != nchunks - 2 or x2d is None:
@@ -1178,6 +1201,8 @@ def _zero_phase_stream(fir, iir, layout, pipe, flying, first, chunks, taps, cs, 
     dev.chain_zp_finish(fir, iir, x2d[:, :m], out=ys[k - 1][:, cs - shift:])
     off = lcut & 1                                            # chunk views on even columns
     n_last = total - (nchunks - 1) * cs
+    if pipe is None and not stays:
+        x2d = x2d.clone()                                     # (read again below, after the next pull)
     last = next(chunks, None)
     while last is not None and last.shape[layout.axis] == 0:
         last = next(chunks, None)
@@ -1241,6 +1266,7 @@ def _zero_phase_stream(fir, iir, layout, pipe, flying, first, chunks, taps, cs, 
         yield pipe.restore(out)
 
 
+@sources.fresh
 @dev.chain_aware
 def sosfiltfilt(pro, sos, axis):
     """Forward-backward (zero-phase) cascaded-biquad filter
@@ -1295,7 +1321,8 @@ def sosfiltfilt(pro, sos, axis):
                 if lag >= 0 and cs >= max(4 * lag, stream.warm_len + lag, 2 * dev.chain_zp_min_chunk(ident, stream)):
                     yield from _zero_phase_stream(ident, stream, layout, pipe, flying, first, chunks,
                                                   np.array([1.0, 0.0]), cs, total, 0, 1, lag,
-                                                  first.device if pipe is None else "cuda", what="sosfiltfilt")
+                                                  first.device if pipe is None else "cuda", what="sosfiltfilt",
+                                                  stays=sources.stays_put(pro))
                     return
             finally:
                 ident.close()
@@ -1419,6 +1446,7 @@ def _ba_zi_to_sos_zi(zi, order, sos, axis):
     return np.moveaxis(states, -1, ax + 1)
 
 
+@sources.fresh
 def lfilter(pro, coeffs, axis, zi=None):
     """Transfer-function (b, a) forward filter with carried state
     (core/numerical.py:414-446), run on the device as a biquad cascade (see
@@ -1432,6 +1460,7 @@ def lfilter(pro, coeffs, axis, zi=None):
     yield from sosfilt(pro, sos, axis, zi=zi)
 
 
+@sources.fresh
 def filtfilt(pro, coeffs, axis):
     """Transfer-function forward-backward filter (core/numerical.py:449-520):
     the same chunk-local scheme as ``sosfiltfilt`` started from the
@@ -1489,6 +1518,7 @@ def _resample_padded(h, L, M, n):
     return taps, half + pre
 
 
+@sources.fresh
 @dev.chain_aware
 def polyphase_resample(pro, L, M, fs, fir, axis, **kwargs):
     """Rational L/M resampling of a producer (core/numerical.py:523-632) on
@@ -1523,7 +1553,11 @@ def polyphase_resample(pro, L, M, fs, fir, axis, **kwargs):
                 _chain_first(cur, chunks), lambda x2d, last: stream.push(x2d, final=last),
                 tell_last=True)
             return
+        # (the kernel wants to know whether a chunk is the last one: the next one is pulled first,
+        # so the chunk of a source whose chunks may be written again is copied before that)
+        keep = (lambda c: c) if sources.stays_put(pro) else dev.copy
         while cur is not None:
+            cur = keep(cur)
             nxt = next(chunks, None)
             x2d, host = layout.to2d(cur)
             y = stream.push(x2d, final=nxt is None)
@@ -1662,6 +1696,9 @@ def _batched(pro, axis, nch):
         for start in range(0, n, target):
             yield slice_along_axis(pro.data, start, min(start + target, n), axis=axis)
         return
+    if not sources.stays_put(pro):
+        yield from pro                  # (each chunk used before the next is pulled: it may be rewritten)
+        return
     buf, count = [], 0
     for arr in pro:
         buf.append(arr)
@@ -1673,6 +1710,7 @@ def _batched(pro, axis, nch):
         yield buf[0] if len(buf) == 1 else dev.concatenate(buf, axis)
 
 
+@sources.fresh
 @dev.chain_aware
 def _spectra_estimatives(pro, fs, nfft, window, overlap, axis, detrend,
                          scaling, func, **kwargs):

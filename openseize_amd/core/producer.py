@@ -22,7 +22,7 @@ from collections import abc as cabc
 import numpy as np
 
 from openseize_amd import _device as dev
-from openseize_amd.core import resources
+from openseize_amd.core import resources, sources
 from openseize_amd.core.arraytools import normalize_axis
 from openseize_amd.core.queues import FIFOArray
 
@@ -185,7 +185,17 @@ class GenProducer(Producer):
     """Re-chunks whatever a generating function yields into exactly
     ``chunksize`` samples (core/producer.py:298-376): pieces are collected
     until at least one chunk is available, full chunks are emitted, the
-    leftover is kept; a non-empty remainder is yielded at the end."""
+    leftover is kept; a non-empty remainder is yielded at the end.
+
+    The chunks are memory of this producer's own: every piece is copied as it
+    arrives, because a function may fill one buffer, yield it and fill it again
+    (core/sources.py).  No copy is made when the function is one of this
+    library's computing generators, whose pieces are new memory already, or a
+    pass-through stage over a source whose chunks stay put.  Divergence: the
+    reference joins pieces with ``np.concatenate`` (:346-358), which copies
+    pieces of at least ``chunksize`` samples but leaves a smaller piece aliased
+    in its queue, so a reused buffer of fewer samples than a chunk comes out
+    wrong there and right here."""
 
     def __init__(self, data, chunksize, axis, shape, **kwargs):
         if shape is None:
@@ -200,10 +210,11 @@ class GenProducer(Producer):
 
     def __iter__(self):
         fifo = FIFOArray(self.chunksize, self.axis)
+        own = not sources.fresh_output(self.data)
         # (dev.run_generating: a generating function of this library hands CUDA tensors
         # on when this producer's direct consumer is another one of them)
         for piece in dev.run_generating(self, self.data, self.kwargs):
-            fifo.put(piece)
+            fifo.put(dev.copy(piece) if own else piece)
             while fifo.full():
                 yield fifo.get()
         if not fifo.empty():

@@ -18,7 +18,7 @@ import numpy as np
 
 from openseize_amd import _device as dev
 from openseize_amd import _lib
-from openseize_amd.core import arraytools
+from openseize_amd.core import arraytools, sources
 from openseize_amd.core.producer import Producer, producer
 
 
@@ -35,6 +35,7 @@ def pad(pro, amt, axis, value=0):
                     shape=grown)
 
 
+@sources.relay
 @dev.chain_aware
 def _production_axis_padder(pro, amt, axis, value):
     """Only the first and last produced arrays change
@@ -54,6 +55,7 @@ def _production_axis_padder(pro, amt, axis, value):
     yield dev.zeros_like_kind(ref, right_shape, value)
 
 
+@sources.fresh
 @dev.chain_aware
 def _other_axis_padder(pro, amt, axis, value):
     """Every produced array grows along a non-production axis
@@ -82,6 +84,7 @@ def squeeze(pro, axis=None):
                     kept.index(pro.axis), shape=tuple(pro.shape[i] for i in kept))
 
 
+@sources.relay
 @dev.chain_aware
 def _map_gen(pro, func):
     for arr in pro:
@@ -134,6 +137,7 @@ def _apply(op, arr, axis, a, b=None):
     return layout.from2d(dev.ew(op, x2d, a2, b2, kind), host)
 
 
+@sources.fresh
 @dev.chain_aware
 def _arith_gen(pro, other, op, verb):
     """pro (op) other, chunk by chunk: ``other`` is a number, an array that
@@ -205,6 +209,7 @@ def multiply_along_axis(pro, arr, axis):
     return _same_shape_producer(pro, partial(_scale_gen, pro, factors.astype(np.float64), along))
 
 
+@sources.fresh
 @dev.chain_aware
 def _scale_gen(pro, factors, along):
     laid = [1] * pro.ndim
@@ -337,6 +342,7 @@ def standardize(pro, axis=-1, ignore_nan=True):
     return _same_shape_producer(pro, partial(_standardize_rows, pro, mu, sd))
 
 
+@sources.fresh
 @dev.chain_aware
 def _standardize_rows(pro, mu, sd):
     import torch
@@ -347,6 +353,7 @@ def _standardize_rows(pro, mu, sd):
         yield layout.from2d(dev.ew(_lib.EW_STANDARDIZE, x2d, a, b, _lib.BCAST_ROW), host)
 
 
+@sources.fresh
 @dev.chain_aware
 def _standardize_chunks(pro, ax, ignore_nan):
     for arr in pro:

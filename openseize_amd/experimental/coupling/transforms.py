@@ -10,6 +10,7 @@ import abc
 from functools import partial
 
 from openseize_amd import _device as dev
+from openseize_amd.core import sources
 from openseize_amd.core.producer import producer
 from openseize_amd.filtering.special import Hilbert
 
@@ -38,6 +39,7 @@ class Transform(abc.ABC):
             part = dev.magphase(z2d, want_mag=which == 0, want_phase=which == 1)[which]
             yield layout.from2d(part, host)
 
+    @sources.fresh
     def _envelope(self):
         yield from self._polar(0)
 
@@ -45,6 +47,7 @@ class Transform(abc.ABC):
     def amplitudes(self):
         return producer(self._envelope, self.chunksize, self.axis, shape=self.signal.shape)
 
+    @sources.fresh
     def _phase(self):
         yield from self._polar(1)
 
@@ -80,6 +83,7 @@ def _complex_rows(arr, layout):
     return t.reshape(layout.nch, t.shape[-1]).contiguous(), host
 
 
+@sources.fresh
 def _join_complex(real_pro, imag_pro):
     """Generator of re + 1j * im over two equally chunked producers, joined on
     the device (``osz_complex_join``)."""
