@@ -1,10 +1,10 @@
 // ab_chain.cpp -- the headline step (1024-tap FIR -> 6-section band-pass sosfiltfilt, 256 ch x 2^20,
 // one osz_chain_zp_step per chunk) timed on several builds of the library in one process, the builds
-// taking turns: A/B/C... of kernel variants on ONE box within seconds of each other.
+// taking turns: A/B/C... of library builds on ONE box within seconds of each other.
 //   g++ -O2 -std=c++17 benchmarks/ab_chain.cpp -o benchmarks/bin/ab_chain -ldl -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -L/opt/rocm/lib -lamdhip64
 //   benchmarks/bin/ab_chain [-c channels] [-r rounds] libA.so libB.so ...
 // Per build: median and best ms per step over the rounds (each round: 12 untimed + 30 timed steps),
-// and a checksum of the last output chunk (variants that must not change results print the same).
+// and a checksum of the last output chunk (builds that must not change results print the same).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -27,8 +27,6 @@ struct Lib {
     int (*zp_step)(h_t, h_t, const double *, int64_t, int64_t, double *, int64_t, int64_t, double *, int64_t, void *);
     int (*sos_set_state)(h_t, const double *);
     const char *(*last_error)();
-    int (*dbg_clk)(unsigned long long *) = nullptr;   // diagnostic builds: shader / 100 MHz clock ticks of one workgroup's life
-    double ghz = 0.0;
     h_t fir = nullptr, sos = nullptr;
     int64_t lag = 0;
     std::vector<float> ms;
@@ -80,7 +78,6 @@ int main(int argc, char **argv) {
         sym(L.dl, "osz_chain_zp_open", L.zp_open);
         sym(L.dl, "osz_chain_zp_step", L.zp_step);
         sym(L.dl, "osz_last_error", L.last_error);
-        L.dbg_clk = reinterpret_cast<int (*)(unsigned long long *)>(dlsym(L.dl, "osz_dbg_clk"));
         libs.push_back(L);
     }
     double *x[3], *y[2];
@@ -133,10 +130,6 @@ int main(int argc, char **argv) {
             float ms;
             hipEventElapsedTime(&ms, e0, e1);
             L.ms.push_back(ms / 30);
-            if (L.dbg_clk) {
-                unsigned long long c[4] = {0, 0, 0, 0};
-                if (L.dbg_clk(c) == 0 && c[1]) L.ghz = (double)c[0] / (double)c[1] * 0.1;
-            }
             if (r == rounds - 1) {
                 std::vector<double> out((size_t)n);
                 hipMemcpy(out.data(), y[(k - 1) & 1] + 5 * n, n * 8, hipMemcpyDeviceToHost);   // channel 5 of the last chunk
@@ -151,7 +144,6 @@ int main(int argc, char **argv) {
         printf("%-40s lag %4lld  median %.4f  best %.4f ms  (", L.path, (long long)L.lag, m[m.size() / 2], m[0]);
         for (float v : L.ms) printf(" %.4f", v);
         printf(" )  sum %.12e", L.sum);
-        if (L.ghz > 0.0) printf("  shader clock %.3f GHz", L.ghz);
         printf("\n");
     }
     return 0;

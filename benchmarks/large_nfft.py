@@ -1,6 +1,6 @@
 """Welch PSD (mean mode) and STFT segments for transform lengths whose half is beyond the LDS:
 the pairs-of-sub-transforms kernel (csrc/specsplit.h) beside the staging route (spec_prep ->
-rocFFT -> spec_post, OSZ_SPEC_SPLIT=0), 256 ch x 2^20 (PSD) / 2^18 (STFT), 50 % overlap.
+rocFFT -> spec_post, OSZ_SPEC_MIX=0), 256 ch x 2^20 (PSD) / 2^18 (STFT), 50 % overlap.
 One JSON line per length; lengths left to rocFFT (a large prime in the way) are marked."""
 import json
 import os
@@ -40,9 +40,8 @@ def main():
         for mode, name, xx in ((_lib.SPEC_PSD_MEAN, "psd", x), (_lib.SPEC_DFT_SEGMENTS, "stft", x[:, : 1 << 18])):
             for route, env in (("on_chip", None), ("staging", "0")):
                 if env:
-                    os.environ["OSZ_SPEC_SPLIT"] = os.environ["OSZ_SPEC_MIX"] = env
+                    os.environ["OSZ_SPEC_MIX"] = env
                 sp = dev.SpecStream(nf, nf, nf // 2, wn, sc, "constant", mode, CH)
-                os.environ.pop("OSZ_SPEC_SPLIT", None)
                 os.environ.pop("OSZ_SPEC_MIX", None)
                 row[f"{name}_{route}_ms"] = round(timed(lambda: sp.push(xx), 5) * 1e3, 3)
                 sp.close()

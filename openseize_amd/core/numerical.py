@@ -219,11 +219,8 @@ def oaconvolve(pro, window, axis, mode, nfft_factor=32):
     non-finite as a whole -- and only when a probe trips: the exact non-finite inputs are looked
     up in the chunks kept by reference (``_Tee``), samples that are non-finite here but finite in
     the reference are computed again from a cleaned copy, and the reference's segments are laid
-    over the piece.  ``OSZ_FIR_REACH=0``: the kernels' own reach (rounds 1-4).
+    over the piece.
     """
-    if os.environ.get("OSZ_FIR_REACH", "1") == "0":
-        yield from _oaconvolve_stream(pro, window, axis, mode, nfft_factor)
-        return
     import torch
     taps = np.asarray(window, dtype=np.float64)
     nsamples = pro.shape[axis]
@@ -673,8 +670,7 @@ def _sosfilt_after_fir(pro, source, taps, nfft_factor, sos, zi):
             # states before them (device snapshots) -- and when a probe trips the stream goes on, from
             # the oldest piece still here, the slow exact way: FIR of the cleaned chunk, the
             # reference's segments laid over its output, the cascade behind that (which loses the
-            # channel by itself).  OSZ_CHAIN_REACH=0: the kernels' own reach.
-            reach = os.environ.get("OSZ_CHAIN_REACH", "1") != "0"
+            # channel by itself).
             step = _oa_reference_step(total, wlen, nfft_factor)
             pend, kept = deque(), deque()              # [j, piece, first 'full' sample, probe]; [k, chunk, states before it]
             slow = {"on": False, "out": deque(), "queue": deque(), "seen": 0, "parts": [], "have": 0,
@@ -787,8 +783,6 @@ def _sosfilt_after_fir(pro, source, taps, nfft_factor, sos, zi):
                     at["k"] = k + 1
                     slow_feed(k, x2d)
                     return release(False)
-                if not reach:
-                    return fused(x2d)
                 # (a host-fed chunk sits in a staging buffer that is written again, and a source whose
                 # chunks do not stay put may write its chunk again: a copy is kept.  The
                 # handles' states before every fourth push: reading them makes the forward link settle its
@@ -823,9 +817,6 @@ def _sosfilt_after_fir(pro, source, taps, nfft_factor, sos, zi):
                 if lcut:
                     iir.forward(fir.flush(device, skip=0, drop=rcut), out=cur[:, last:last + lcut])
                 y = cur[:, lcut:last + lcut]
-                if not reach:
-                    yield hand_on(y)
-                    return
                 pend.append([nchunks - 1, y, (nchunks - 1) * cs + lcut, watch.add(_probe_sum(y))])
                 while pend and not slow["on"]:
                     y = release(True)
@@ -909,11 +900,10 @@ def _sosfiltfilt_after_fir(pro, source, taps, nfft_factor, sos):
             pipe = None if resident else dev.HostPipe(layout)
             flying = deque()
             if one_kernel:
-                # (the reference FIR's NaN reach, segment by segment; OSZ_ZP_REACH=0: the kernels' own,
-                # from the sample itself)
-                reach = 0 if os.environ.get("OSZ_ZP_REACH") == "0" else _oa_reference_step(total, wlen, nfft_factor)
+                # (the reference FIR's NaN reach, segment by segment)
                 yield from _zero_phase_stream(fir, iir, layout, pipe, flying, first, chunks, taps, cs, total,
-                                              lcut, rcut, lag, device, ref_step=reach,
+                                              lcut, rcut, lag, device,
+                                              ref_step=_oa_reference_step(total, wlen, nfft_factor),
                                               stays=sources.stays_put(source))
                 return
 
@@ -1538,12 +1528,9 @@ def polyphase_resample(pro, L, M, fs, fir, axis, **kwargs):
 
     layout = dev.Layout(pro.shape, axis)
     # the window as resample_poly filters with it: zeros in front and behind (a non-finite sample is
-    # then lost to the outputs SciPy -- the reference -- loses it to; OSZ_POLY_PAD=0: the bare window)
-    if os.environ.get("OSZ_POLY_PAD", "1") != "0":
-        taps, centre = _resample_padded(h, int(L), int(M), int(pro.shape[axis]))
-        stream = dev.PolyStream(taps, int(L), int(M), layout.nch, centre=centre)
-    else:
-        stream = dev.PolyStream(h, int(L), int(M), layout.nch)
+    # then lost to the outputs SciPy -- the reference -- loses it to)
+    taps, centre = _resample_padded(h, int(L), int(M), int(pro.shape[axis]))
+    stream = dev.PolyStream(taps, int(L), int(M), layout.nch, centre=centre)
     try:
         chunks = iter(pro)
         cur = next(chunks, None)

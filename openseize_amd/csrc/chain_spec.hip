@@ -45,7 +45,6 @@
 // into a carry (spec_import) by filtering the pending FIR tail.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <functional>
 #include <vector>
 
@@ -448,43 +447,37 @@ static int spec_build(ChainSpec *s) {
     // where the right tail's bursts are cut: the library's default unless the caller set one
     // (osz_chain_zp_tolerance names both links of a cascade)
     const spec::ld_t tol = sos->zp_tol > 0.0 ? (spec::ld_t)sos->zp_tol : spec::kTailTol;
-    // one real block per transform where its tables exist (OSZ_SPEC_NEGA=0: the pair kernel below)
-    static const bool nega_on = [] {
-        const char *e = getenv("OSZ_SPEC_NEGA");
-        return !(e && e[0] == '0');
-    }();
-    if (nega_on) {
-        const bool forgets = sos->warm_len <= (1 << 20);
-        const spec::TablesZp Tn = spec::kept_tables(spec::kKeptSpecn, fir->htaps, sos->coef, nsec, (double)tol, forgets, [&] {
-            return spec::build_specn(fir->htaps.data(), wlen, sos->coef, nsec, forgets, 15360 - 1024, tol);
-        });
-        if (Tn.eligible) {
-            const size_t nl = (size_t)Tn.NM * 2;               // lambda^256: row 1 of the table
-            std::vector<double> cat(Tn.L.begin() + nl, Tn.L.begin() + 2 * nl);
-            cat.insert(cat.end(), Tn.P.begin(), Tn.P.end());
-            cat.insert(cat.end(), Tn.M.begin(), Tn.M.end());
-            if ((rcu = up(&s->dH, spec_permuted_spectrum(Tn.H))) || (rcu = up(&s->dT, cat))) return rcu;
-            const size_t cbn = sizeof(double) * (size_t)fir->nch * kSpecLdc;
-            for (int q = 0; q < 2; ++q) {
-                OSZ_HIP(hipMalloc(&s->dcarry[q], cbn));
-                OSZ_HIP(hipMemset(s->dcarry[q], 0, cbn));
-            }
-            s->hist_cap = (wlen - 1) + (int)sos->warm_len;
-            for (int q = 0; q < 2; ++q)
-                OSZ_HIP(hipMalloc(&s->dhist[q], sizeof(double) * (size_t)fir->nch * s->hist_cap));
-            OSZ_HIP(hipMalloc(&s->dsnap_fir, sizeof(double) * (size_t)fir->nch * (wlen - 1)));
-            OSZ_HIP(hipMalloc(&s->dsnap_sos, sizeof(double) * (size_t)nsec * fir->nch * 2));
-            s->NR = Tn.NR;
-            s->NM = Tn.NM;
-            s->NS = Tn.NS;
-            s->R = Tn.R;
-            s->nh = Tn.nh;
-            s->nega = true;
-            s->eligible = true;
-            return OSZ_OK;
+    // one real block per transform where its tables exist, the pair kernel below where they do not
+    const bool forgets = sos->warm_len <= (1 << 20);
+    const spec::TablesZp Tn = spec::kept_tables(spec::kKeptSpecn, fir->htaps, sos->coef, nsec, (double)tol, forgets, [&] {
+        return spec::build_specn(fir->htaps.data(), wlen, sos->coef, nsec, forgets, 15360 - 1024, tol);
+    });
+    if (Tn.eligible) {
+        const size_t nl = (size_t)Tn.NM * 2;               // lambda^256: row 1 of the table
+        std::vector<double> cat(Tn.L.begin() + nl, Tn.L.begin() + 2 * nl);
+        cat.insert(cat.end(), Tn.P.begin(), Tn.P.end());
+        cat.insert(cat.end(), Tn.M.begin(), Tn.M.end());
+        if ((rcu = up(&s->dH, spec_permuted_spectrum(Tn.H))) || (rcu = up(&s->dT, cat))) return rcu;
+        const size_t cbn = sizeof(double) * (size_t)fir->nch * kSpecLdc;
+        for (int q = 0; q < 2; ++q) {
+            OSZ_HIP(hipMalloc(&s->dcarry[q], cbn));
+            OSZ_HIP(hipMemset(s->dcarry[q], 0, cbn));
         }
+        s->hist_cap = (wlen - 1) + (int)sos->warm_len;
+        for (int q = 0; q < 2; ++q)
+            OSZ_HIP(hipMalloc(&s->dhist[q], sizeof(double) * (size_t)fir->nch * s->hist_cap));
+        OSZ_HIP(hipMalloc(&s->dsnap_fir, sizeof(double) * (size_t)fir->nch * (wlen - 1)));
+        OSZ_HIP(hipMalloc(&s->dsnap_sos, sizeof(double) * (size_t)nsec * fir->nch * 2));
+        s->NR = Tn.NR;
+        s->NM = Tn.NM;
+        s->NS = Tn.NS;
+        s->R = Tn.R;
+        s->nh = Tn.nh;
+        s->nega = true;
+        s->eligible = true;
+        return OSZ_OK;
     }
-    const spec::Tables T = spec::build(fir->htaps.data(), wlen, sos->coef, nsec, sos->warm_len <= (1 << 20), tol);
+    const spec::Tables T = spec::build(fir->htaps.data(), wlen, sos->coef, nsec, forgets, tol);
     if (!T.eligible) return OSZ_OK;
     if ((rcu = up(&s->dH, spec_permuted_spectrum(T.H))) || (rcu = up(&s->dM, T.M)) || (rcu = up(&s->dP, T.P)) || (rcu = up(&s->dL, T.L)))
         return rcu;

@@ -32,7 +32,6 @@
 // stream never exists); SURVEY 8d books the chain at 48.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <functional>
 #include <mutex>
 #include <utility>
@@ -191,48 +190,8 @@ __device__ __forceinline__ void zp_bwd_bursts(double *re, double *im, double *c7
     }
 }
 
-// In-kernel phase stamps for the diagnostic build only (benchmarks/zp_stamps.hip defines
-// OSZ_FIR_STAMPS); the library build has none.  Slots 0-11: FirPair's; 12-15: this kernel's.
-#ifdef OSZ_FIR_STAMPS
-#define OSZ_ZSTAMP(slot)                                                             \
-    do {                                                                             \
-        unsigned long long now_;                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                           \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory"); \
-        __builtin_amdgcn_sched_barrier(0);                                           \
-        zst[slot] += now_ - P.stamp_last;                                            \
-        P.stamp_last = now_;                                                         \
-    } while (0)
-#else
-#define OSZ_ZSTAMP(slot) do { } while (0)
-#endif
-
-// Absolute time marks of a workgroup (diagnostic build only: benchmarks/zp_timeline.hip defines
-// OSZ_ZP_MARKS): entry, tables in LDS, whole pairs done, chunk closed, exit.
-#ifdef OSZ_ZP_MARKS
-__device__ unsigned long long *g_zp_marks = nullptr;   // [nch][nruns][8]
-#define OSZ_ZMARK(k)                                                                            \
-    do {                                                                                        \
-        if (g_zp_marks && threadIdx.x == 0) {                                                   \
-            unsigned long long now_;                                                            \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory");        \
-            g_zp_marks[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (k)] = now_;        \
-        }                                                                                       \
-    } while (0)
-#else
-#define OSZ_ZMARK(k) do { } while (0)
-#endif
-
 template <int NR, int NM, bool DMA = false>
 __global__ __launch_bounds__(256, 2) void chain_zp_kernel(ZpArgs g) {
-    OSZ_ZMARK(0);
-#ifdef OSZ_ZP_MARKS
-    if (g_zp_marks && threadIdx.x == 0) {
-        unsigned long long rt;
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt)::"memory");
-        g_zp_marks[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + 6] = rt;
-    }
-#endif
     constexpr int D = 16 - NR, S = 256 * NR;
     extern __shared__ fft::cube::C2 cube_lds[];
     const int R = g.R, Rf = g.Rf, nh = g.nh, ns = 2 * nh;
@@ -284,7 +243,6 @@ __global__ __launch_bounds__(256, 2) void chain_zp_kernel(ZpArgs g) {
     int younger = -1;                // DMA kernels: vector-memory operations behind the pending requests
     const unsigned lane8_entry = 8u * (unsigned)t;   // a lane's byte offset inside a row of 256 samples
     __syncthreads();
-    OSZ_ZMARK(1);
 
     // a sample of the chunk (position i, value v) goes to the output, L samples late, or,
     // the chunk's last L samples, to `held`
@@ -296,12 +254,6 @@ __global__ __launch_bounds__(256, 2) void chain_zp_kernel(ZpArgs g) {
         else ho[q_ - n] = (v_);                 \
     } while (0)
 
-#ifdef OSZ_FIR_STAMPS
-    unsigned long long zst[16];
-    for (int q = 0; q < 16; ++q) zst[q] = 0;
-    for (int q = 0; q < 12; ++q) P.stamp_acc[q] = 0;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(P.stamp_last)::"memory");
-#endif
     for (int p = first; p <= lastf; ++p) {
         const int64_t o = (int64_t)p * (2 * S);
         double re[16], im[16];
@@ -329,7 +281,6 @@ __global__ __launch_bounds__(256, 2) void chain_zp_kernel(ZpArgs g) {
                 im[j] = j < NR ? buf_load(rx, lane8_entry, 2048u * (j + NR)) : 0.0;
             }
         }
-        OSZ_ZSTAMP(0);    // previous pair's stores + this pair's loads issued
         P.transform(re, im);
         if (DMA && p < lastf) {
             // inverse pass 1 has read this wave's pieces of the cube (its values are in use
@@ -338,7 +289,6 @@ __global__ __launch_bounds__(256, 2) void chain_zp_kernel(ZpArgs g) {
             zp_request_rows<NR>(xr + o + 2 * S, 2 * NR, t, cube_lds);
         }
         int nst = 0;             // row stores of this pair, -1: some went another way
-        OSZ_ZSTAMP(11);   // inverse pass 1
         // thread -> role indices, recomputed per pair from an opaque copy of t
         int tt = t;
         asm volatile("" : "+v"(tt));
@@ -356,14 +306,11 @@ __global__ __launch_bounds__(256, 2) void chain_zp_kernel(ZpArgs g) {
             im[j] += re[j + NR];
             P.cr[j] = im[j + NR];
         }
-        OSZ_ZSTAMP(12);   // fit samples to LDS, overlap add
         __syncthreads();
-        OSZ_ZSTAMP(13);   // barrier
         // fit and amplitudes: this pair's into kapA, block b's also into the other half of
         // kapP for the next pair
         zp_fit_kappa<NM>(tt, nh, R, fitbuf, mtab, lrow, kapA, kapP + (par ^ 1) * (2 * R * NM * 2));
         __syncthreads();
-        OSZ_ZSTAMP(14);   // fit + amplitudes + barrier
         const double *kap = kapA, *kpb = kapP + par * (2 * R * NM * 2);
         // Six burst evaluations per row index r serve the eight places a burst lands: the
         // wrapped right tail of block a leaves its row r and arrives, one window on, in row
@@ -402,7 +349,6 @@ __global__ __launch_bounds__(256, 2) void chain_zp_kernel(ZpArgs g) {
                 default: zp_bwd_bursts<NR, NM, 5>(re, im, c7, kap, kpb, R, Pr, Pi); break;
             }
         }
-        OSZ_ZSTAMP(15);   // bursts
         const double qn = spec_qnan();
         const bool own = p >= p0 && p < p1;
         const bool edge = p == g.W - 1;        // its samples may be among the chunk's last L
@@ -474,16 +420,6 @@ __global__ __launch_bounds__(256, 2) void chain_zp_kernel(ZpArgs g) {
         younger = nst;
     }
 
-#ifdef OSZ_FIR_STAMPS
-    if (g_fir_stamps && (t & 63) == 0) {
-        unsigned long long *so = g_fir_stamps + (((int64_t)c * g.nruns + run) * 4 + (t >> 6)) * 16;
-        for (int q = 1; q <= 10; ++q) so[q] = P.stamp_acc[q];
-        so[0] = zst[0];
-        so[11] = zst[11];
-        for (int q = 12; q < 16; ++q) so[q] = zst[q];
-    }
-#endif
-    OSZ_ZMARK(2);
     if (run == g.nruns - 1) {
         // ---- the closing pair: blocks of la and lb samples (lb > 0 only behind a whole
         // block a), accumulated in LDS over the idle cube: acc[i], i = samples from its start
@@ -577,25 +513,13 @@ __global__ __launch_bounds__(256, 2) void chain_zp_kernel(ZpArgs g) {
         }
     }
 #undef OSZ_ZP_PUT
-    OSZ_ZMARK(3);
     // where the forward stream of this channel first went bad: every later launch starts bad
     // (above), and osz_chain_zp_seal makes the chunks the reference loses NaN as a whole --
     // this chunk (also the runs behind this one, which do not see it) and the one before.
     // (No sealing of the later runs in here: overwriting what workgroups on other XCDs have
     // written wants an agent-scope release from each of them, a write-back of the XCD's L2 --
-    // 12 us per workgroup on average, 50 at the worst, benchmarks/zp_timeline.hip.)
+    // 12 us per workgroup on average, 50 at the worst, profiles/r03_zp_timeline.txt.)
     if (bad && bad_at >= 0 && t == 0) atomicMin(reinterpret_cast<long long *>(g.nanpos + c), g.pos + bad_at);
-    OSZ_ZMARK(4);
-#ifdef OSZ_ZP_MARKS
-    if (g_zp_marks && threadIdx.x == 0) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hw), "=s"(xcc));
-        g_zp_marks[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + 5] = ((unsigned long long)xcc << 32) | hw;
-        unsigned long long rt;
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt)::"memory");
-        g_zp_marks[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + 7] = rt;
-    }
-#endif
 }
 
 // NaN reach of sosfiltfilt (sos_tile.h): a chunk of the reference's output is NaN as a
@@ -661,15 +585,6 @@ struct ChainZp {
     int64_t ref_step = 0;          // osz_chain_zp_reach: the reference FIR's segment length (0: none)
 };
 
-// OSZ_ZP_NEGA=0: the pair kernel of this file instead of chain_zpn.hip's (one real block per
-// transform), for comparison
-static bool zp_nega() {
-    static const bool on = [] {
-        const char *e = getenv("OSZ_ZP_NEGA");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
 // the shortest chunk a step takes: two pairs of blocks / two blocks
 static int64_t zp_min_chunk(const ChainZp *s) { return (s->nega ? 2 : 4) * 256 * (int64_t)s->NR; }
 
@@ -719,19 +634,18 @@ static int zp_get(osz_fir_s *fir, osz_sos_s *sos, ChainZp **out) {
         s->sos = sos;
         fir->zp = sos->zp = s;
         if (fir->parts.size() == 1 && fir->nch == sos->nch) {
-            spec::TablesZp T;
             const double tol = sos->zp_tol > 0.0 ? sos->zp_tol : (double)spec::kTailTol;
-            if (zp_nega()) {
-                const bool forgets = sos->warm_len <= (1 << 20);
-                T = spec::kept_tables(spec::kKeptZpn, fir->htaps, sos->coef, sos->nsec, tol, forgets, [&] {
-                    return spec::build_zpn(fir->htaps.data(), fir->ntaps, sos->coef, sos->nsec, forgets, 15360 - 1024,
-                                           (spec::ld_t)tol);
-                });
-                s->nega = T.eligible;
-            }
+            const bool forgets = sos->warm_len <= (1 << 20);
+            // one real block per transform (chain_zpn_body.h) where its tables are eligible, the
+            // pair kernel of this file where they are not
+            spec::TablesZp T = spec::kept_tables(spec::kKeptZpn, fir->htaps, sos->coef, sos->nsec, tol, forgets, [&] {
+                return spec::build_zpn(fir->htaps.data(), fir->ntaps, sos->coef, sos->nsec, forgets, 15360 - 1024,
+                                       (spec::ld_t)tol);
+            });
+            s->nega = T.eligible;
             if (!T.eligible)
-                T = spec::build_zp(fir->htaps.data(), fir->ntaps, sos->coef, sos->nsec, sos->warm_len <= (1 << 20),
-                                   15360, (spec::ld_t)tol);
+                T = spec::build_zp(fir->htaps.data(), fir->ntaps, sos->coef, sos->nsec, forgets, 15360,
+                                   (spec::ld_t)tol);
             if (T.eligible) {
                 auto up = [](double **d, const std::vector<double> &v) -> int {
                     OSZ_HIP(hipMalloc(d, v.size() * sizeof(double)));

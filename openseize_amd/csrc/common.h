@@ -100,16 +100,13 @@ __device__ __forceinline__ void wave_lds_fence() {
 // The two workgroups of a CU (the 256-thread kernels that fill it with two: one wave of each
 // per SIMD) do not get equal shares by themselves: the issue arbiter serves the older wave
 // first, the workgroup placed second runs ~20 % behind and then finishes alone on a half-empty
-// CU (benchmarks/zp_timeline.hip).  Each wave therefore raises and drops its priority in turn
+// CU (profiles/r03_zp_timeline.txt).  Each wave therefore raises and drops its priority in turn
 // with the other wave of its SIMD (they differ in the lowest bit of their wave slot),
 // switching on bit 18 of the shader clock (~130 us; 12 ... 20 measured).  Long launches at
 // full width gain nothing (the chip runs at the clock its power allows either way), short and
 // narrow ones do: the zero-phase chain at 32 channels 297 -> 266 us (the overlap-add FIR and
 // the Welch kernel measured no different with it and stay without).
 __device__ __forceinline__ void take_turns() {
-#ifdef OSZ_NO_TURNS   // diagnostic builds only: the arbiter's own order
-    return;
-#endif
     unsigned slot;
     unsigned long long now;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 1)" : "=s"(slot));
@@ -142,11 +139,7 @@ __device__ __forceinline__ buf_d2 buf_load2(__amdgpu_buffer_rsrc_t r, unsigned l
 // bit 1 = `nt` -- they do not displace the spectrum in L2 / the Infinity Cache; with the same hint
 // on the rows' LDS-DMA requests the zero-phase chain runs 2 % faster, profiles/README.md round 5)
 __device__ __forceinline__ void buf_store(double v, __amdgpu_buffer_rsrc_t r, unsigned lane_bytes, unsigned row_bytes) {
-#ifdef OSZ_NO_NT      // (A/B builds only)
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(buf_u2, v), r, lane_bytes, row_bytes, 0);
-#else
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(buf_u2, v), r, lane_bytes, row_bytes, 2);
-#endif
 }
 
 // rccl.hip: in-place all-reduce(sum) of `count` float64 / int64 elements over

@@ -22,7 +22,6 @@
 //     samples) and written once (8 B): 16 B per channel-sample; the filter
 //     spectrum H (64 KB) and the twiddles live in registers for a whole run.
 #include <cmath>
-#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -62,12 +61,6 @@ __global__ __launch_bounds__(256, 2) void fir_oa_kernel(FirArgs a) {
 
     int64_t blk = blk0;
     for (; blk < P.blk1 && !P.whole(blk); blk += 2) P.any_pair(blk);
-#ifdef OSZ_FIR_STAMPS
-    unsigned long long rt_begin, mt_begin;
-    asm volatile("s_memrealtime %0\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt_begin), "=s"(mt_begin)::"memory");
-    for (int q = 0; q < 12; ++q) P.stamp_acc[q] = 0;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(P.stamp_last)::"memory");
-#endif
     if (PF != 0) {
         // the last whole pair of the run requests itself again (unused, in bounds)
         if (blk < P.blk1 && P.whole(blk)) {
@@ -83,20 +76,6 @@ __global__ __launch_bounds__(256, 2) void fir_oa_kernel(FirArgs a) {
     } else {
         for (; blk < P.blk1 && P.whole(blk); blk += 2) P.fast_pair(blk);
     }
-#ifdef OSZ_FIR_STAMPS
-    if (g_fir_stamps && (t & 63) == 0) {
-        unsigned long long *o = g_fir_stamps + (((int64_t)c * a.nruns + run) * 4 + (t >> 6)) * 12;
-        for (int q = 0; q < 12; ++q) o[q] = P.stamp_acc[q];
-        // clock check: the same interval in shader-clock ticks (s_memtime) and in
-        // constant 100 MHz ticks (s_memrealtime), first workgroup only
-        if (c == 0 && run == 0 && t == 0) {
-            unsigned long long rt1, mt1;
-            asm volatile("s_memrealtime %0\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt1), "=s"(mt1)::"memory");
-            g_fir_clock[0] = mt1 - mt_begin;
-            g_fir_clock[1] = rt1 - rt_begin;
-        }
-    }
-#endif
     for (; blk < P.blk1; blk += 2) P.any_pair(blk);
 
     double *tl = a.tails + ((int64_t)c * a.nruns + run) * P.wm1;
@@ -470,13 +449,8 @@ static int fir_build_part(FirPart &pt, const double *taps, int ntaps, int nch) {
 static int fir_part_push(osz_fir_s *h, FirPart &pt, const double *x, int64_t ldx, int64_t n,
                          double *y, int64_t ldy, int64_t skip, int accum, hipStream_t st) {
     const int wm1 = pt.ntaps - 1;
-    // one real block per transform (fir_nega_kernel) where its tables exist; OSZ_FIR_NEGA=0: the
-    // pair kernel, for comparison
-    static const bool nega_on = [] {
-        const char *e = getenv("OSZ_FIR_NEGA");
-        return !(e && e[0] == '0');
-    }();
-    const bool nega = nega_on && pt.dHn != nullptr && wm1 >= 1;
+    // one real block per transform (fir_nega_kernel) where its tables exist
+    const bool nega = pt.dHn != nullptr && wm1 >= 1;
     const int step = nega ? pt.stepn : pt.step;
     const int64_t nblocks = (n + step - 1) / step;
     // run length: long runs (every workgroup pays for its twiddle loads, its tail

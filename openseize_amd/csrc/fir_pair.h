@@ -9,24 +9,6 @@
 
 namespace osz {
 
-// In-kernel phase stamps for the diagnostic build only
-// (benchmarks/fir_stamps.hip defines OSZ_FIR_STAMPS); the library build has none.
-#ifdef OSZ_FIR_STAMPS
-__device__ unsigned long long *g_fir_stamps = nullptr;   // [waves][12] cycle sums
-__device__ unsigned long long g_fir_clock[2];            // {s_memtime, s_memrealtime} ticks of one run
-#define OSZ_FSTAMP(slot)                                                             \
-    do {                                                                             \
-        unsigned long long now_;                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                           \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory"); \
-        __builtin_amdgcn_sched_barrier(0);                                           \
-        stamp_acc[slot] += now_ - stamp_last;                                        \
-        stamp_last = now_;                                                           \
-    } while (0)
-#else
-#define OSZ_FSTAMP(slot) do { } while (0)
-#endif
-
 constexpr int kFirMaxTaps = 2049;  // NFFT - ntaps + 1 >= ntaps - 1
 
 struct FirArgs {
@@ -104,8 +86,8 @@ struct FirPair {
     // PF, whole pairs: the filter spectrum of the NEXT pair, requested after
     // inverse pass 1 and BEFORE this pair's stores -- requested behind them (as
     // the per-pair spectrum of HPRE does) it cannot be seen to land before they
-    // have drained: one in-order counter (benchmarks/fir_stamps: 2800 ticks of
-    // a 20 000-tick pair).  Same values every pair; the point is WHEN they
+    // have drained: one in-order counter (the kernel's phase stamps: 2800 ticks
+    // of a 20 000-tick pair).  Same values every pair; the point is WHEN they
     // occupy registers: not during the inverse passes, where nx lives.
     typedef double d2_t __attribute__((ext_vector_type(2)));
     d2_t Hn[PF2 ? 16 : 1];
@@ -129,7 +111,7 @@ struct FirPair {
     // only make the compiler's own waits more conservative, never too short.
     // (Spreading the requests of a pair over the three inverse passes instead of
     // one burst behind the multiply -- a burst holds the wave at the issue port
-    // for ~120 cycles per load, benchmarks/fir_stamps -- measured 2 % SLOWER.)
+    // for ~120 cycles per load, the kernel's phase stamps -- measured 2 % SLOWER.)
     __device__ __forceinline__ void request_next(int64_t blk) {
         int64_t off = blk * a.step + t;
         asm volatile("" : "+v"(off));   // per pair: hoisted, 2 NR addresses would spill
@@ -167,9 +149,6 @@ struct FirPair {
 #pragma unroll
         for (int r = 0; r < (PF2 ? 16 : 0); ++r) asm volatile("" : "+v"(Hn[PF2 ? r : 0]));
     }
-#ifdef OSZ_FIR_STAMPS
-    unsigned long long stamp_acc[12], stamp_last;
-#endif
 
     __device__ __forceinline__ bool whole(int64_t blk) const {
         return blk + 1 < blk1 && (blk + 2) * a.step <= a.n && blk * a.step >= a.skip;
@@ -186,9 +165,7 @@ struct FirPair {
         asm volatile("" : "+v"(t));
         if (CUBE2) fft::cube2::f1(t, re, im, tw1, L);
         else fft::cube::f1(t, re, im, tw1, L);
-        OSZ_FSTAMP(1);   // sample loads landed + pass 1 + stores
         __syncthreads();
-        OSZ_FSTAMP(2);   // barrier 1
         if (CUBE2) fft::cube2::f2(t, re, im, tw2, L);
         else fft::cube::f2(t, re, im, tw2, L);
         // HPRE > 0: that many filter-spectrum bins are requested before the barrier
@@ -205,13 +182,10 @@ struct FirPair {
             hr[r] = h.x;
             hi[r] = h.y;
         }
-        OSZ_FSTAMP(3);   // pass 2
         if (CUBE2) wave_lds_fence();
         else __syncthreads();
-        OSZ_FSTAMP(4);   // barrier 2
         if (CUBE2) fft::cube2::f3(t, re, im, L);
         else fft::cube::f3(t, re, im, L);
-        OSZ_FSTAMP(5);   // pass 3
         if (PF2 && REQ) wait_spectrum();
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -225,18 +199,13 @@ struct FirPair {
         }
         // unconditional requests: nx must be dead above this line
         if (PF && REQ) request_next(next_blk);
-        OSZ_FSTAMP(6);   // filter spectrum: loads + multiply
         if (CUBE2) fft::cube2::i3(t, re, im, L);
         else fft::cube::i3(t, re, im, L);
-        OSZ_FSTAMP(7);   // inverse pass 3
         if (CUBE2) wave_lds_fence();
         else __syncthreads();
-        OSZ_FSTAMP(8);   // barrier 3
         if (CUBE2) fft::cube2::i2(t, re, im, tw2, L);
         else fft::cube::i2(t, re, im, tw2, L);
-        OSZ_FSTAMP(9);   // inverse pass 2
         __syncthreads();
-        OSZ_FSTAMP(10);  // barrier 4
         if (CUBE2) fft::cube2::i1(t, re, im, tw1, L);
         else fft::cube::i1(t, re, im, tw1, L);
     }
@@ -271,7 +240,6 @@ struct FirPair {
 #pragma unroll
             for (int r = 0; r < (PF2 ? 16 : 0); ++r) asm volatile("" : "+v"(Hn[PF2 ? r : 0]));
         }
-        OSZ_FSTAMP(0);   // sample loads issued (and the previous pair's stores)
         transform<true>(re, im);
         // re[j] = a[256 j + t], im[j] = b[256 j + t]
 #pragma unroll
@@ -299,8 +267,7 @@ struct FirPair {
                 buf_store(im[j], ry, lane8, 2048u * (j + NR));
             }
         }
-        OSZ_FSTAMP(11);  // inverse pass 1 + overlap add + stores issued
-        wait_next();     // (the stamped build books this wait under the next pair's slot 0)
+        wait_next();
     }
 
     // any pair: ragged lengths, left cut, accumulate

@@ -6,7 +6,7 @@
 // assembly benchmarks/check_async_regions.py finds clean (tests/test_fir_async.py
 // rebuilds the assembly and checks exactly that).  Measured on the BASELINE chunk
 // (1024 taps, 12 rows), same box: 0: 1.078 ms, 1: 1.048-1.052 ms, 2: 1.037-1.044 ms -- variant 2
-// moves the stalls (fir_stamps) and gains under 1 %, so 1 is the default everywhere;
-// OSZ_FIR_PF=0|1|2 overrides the table.
+// moves the stalls (the kernel's phase stamps) and gains under 1 %, so 1 is the
+// default everywhere.
 #pragma once
 #define OSZ_FIR_PF_TABLE {1, 1, 1, 1, 1, 1, 1, 1}

@@ -195,11 +195,7 @@ __global__ __launch_bounds__(NT * EG, 3) void poly_block_kernel(PolyBlockArgs b)
             // taps of this phase stream: the others of its apad are the table's padding -- skipped, not
             // multiplied (0 x NaN is NaN: a non-finite sample reaches the outputs whose TAPS touch it,
             // zero-valued taps of the caller's window included, and no other)
-#ifdef OSZ_POLY_MULPAD     // (A/B builds: the table's padding multiplied as in rounds 1-4)
-            const int cnt = b.apad;
-#else
             const int cnt = ph <= crem ? cq + 1 : cq;      // = (msub - 1 - ph) / M + 1, or 0 behind the taps
-#endif
             const int nfull = cnt & ~(kPolyBlk - 1);
             for (int a0 = 0; a0 < nfull; a0 += kPolyBlk) {
                 double g[kPolyBlk], xv[kPolyBlk + kPolyR - 1];

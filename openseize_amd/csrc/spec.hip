@@ -1282,13 +1282,7 @@ static int specmix_run(osz_spec_s *h, const double *src, int64_t ld, void *out, 
     a.N = h->nfft;
     a.M = h->nfft / 2;
     a.npass = h->mix_npass;
-    {
-        static const bool half_on = [] {           // (OSZ_MIX_HALF=0: every segment sums both its halves, A/B runs)
-            const char *e = getenv("OSZ_MIX_HALF");
-            return !(e && e[0] == '0');
-        }();
-        a.halfcarry = half_on && 2 * h->stride == h->nwin && h->nwin == h->nfft && h->mix_radix[0] % 2 == 0;
-    }
+    a.halfcarry = 2 * h->stride == h->nwin && h->nwin == h->nfft && h->mix_radix[0] % 2 == 0;
     for (int q = 0, B = a.M; q < h->mix_npass; ++q) {
         a.radix[q] = h->mix_radix[q];
         const int S = B / a.radix[q], nblk = a.M / B;
@@ -1336,20 +1330,11 @@ static int specmix_run(osz_spec_s *h, const double *src, int64_t ld, void *out, 
 static bool specsplit_plan(int nfft, int *r0, int *npass, int *radix) {
     if (nfft < 4 || (nfft & 1)) return false;
     const int M = nfft / 2;
-    static const int from = [] {                // (OSZ_SPLIT_FROM: halves above this many points are split, timing runs)
-        const char *e = getenv("OSZ_SPLIT_FROM");
-        return e ? atoi(e) : mix::kMaxM;
-    }();
-    if (M <= from) return false;
-    static const int local_max = [] {           // (OSZ_SPLIT_LOCAL: fewer local points, more workgroups per segment)
-        const char *e = getenv("OSZ_SPLIT_LOCAL");
-        const int v = e ? atoi(e) : 0;
-        return v >= 1282 && v < mix::kMaxSplitLocal ? v : mix::kMaxSplitLocal;
-    }();
+    if (M <= mix::kMaxM) return false;
     for (int R = 2; R <= mix::kMaxSplitR0; ++R) {
         if (M % R) continue;
         const int S0 = M / R;
-        if (2 * S0 > local_max || 2 * S0 <= 1280) continue;      // (three workgroup sizes are built)
+        if (2 * S0 > mix::kMaxSplitLocal || 2 * S0 <= 1280) continue;      // (three workgroup sizes are built)
         int np = 0, rad[mix::kMaxPass];
         if (!specmix_plan(2 * S0, &np, rad) || np + 1 > mix::kMaxPass) continue;
         radix[0] = R;
@@ -1402,13 +1387,7 @@ static int specsplit_run(osz_spec_s *h, const double *src, int64_t ld, void *out
     a.N = h->nfft;
     a.M = h->nfft / 2;
     a.npass = h->mix_npass;
-    {
-        static const bool half_on = [] {
-            const char *e = getenv("OSZ_MIX_HALF");
-            return !(e && e[0] == '0');
-        }();
-        a.halfcarry = half_on && 2 * h->stride == h->nwin && h->nwin == h->nfft && a.M % 2 == 0;
-    }
+    a.halfcarry = 2 * h->stride == h->nwin && h->nwin == h->nfft && a.M % 2 == 0;
     a.radix[0] = R0;
     for (int q = 1, B = S0; q < h->mix_npass; ++q) {
         a.radix[q] = h->mix_radix[q];
@@ -1746,12 +1725,9 @@ int osz_spec_create(osz_spec_t *h, int nwin, int nfft, int stride, const double 
         const char *em = getenv("OSZ_SPEC_MIX");
         p->dtwn = nullptr;
         p->dpos = nullptr;
-        const char *ef = getenv("OSZ_SPLIT_FROM");
-        p->mixed = !p->fused && !p->fused8 && !(em && atoi(em) == 0) && !(ef && nfft / 2 > atoi(ef)) &&
-                   specmix_plan(nfft, &p->mix_npass, p->mix_radix);
-        // its half beyond the LDS: two of its R0 sub-transforms per workgroup (OSZ_SPEC_SPLIT=0: the staging route)
-        const char *es = getenv("OSZ_SPEC_SPLIT");
-        p->split = !p->fused && !p->fused8 && !p->mixed && !(em && atoi(em) == 0) && !(es && atoi(es) == 0) &&
+        p->mixed = !p->fused && !p->fused8 && !(em && atoi(em) == 0) && specmix_plan(nfft, &p->mix_npass, p->mix_radix);
+        // its half beyond the LDS: two of its R0 sub-transforms per workgroup (OSZ_SPEC_MIX=0: the staging route)
+        p->split = !p->fused && !p->fused8 && !p->mixed && !(em && atoi(em) == 0) &&
                    specsplit_plan(nfft, &p->split_r0, &p->mix_npass, p->mix_radix);
         p->split_s0 = p->split ? nfft / 2 / p->split_r0 : 0;
         if (p->mixed || p->split) {

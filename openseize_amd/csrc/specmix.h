@@ -329,11 +329,7 @@ __device__ __forceinline__ void head_finish(C2 *z, const C2 *w1, double mean, do
                 // (with the usual 50 % overlap a first half is read for the last time: it shall not
                 // displace the halves still to come back; a hint, and one in the instruction's encoding:
                 // a run-time choice between the two loads spills)
-#ifdef OSZ_MIX_NO_NT     // (A/B builds only)
-                const bool last_use = false;
-#else
                 const bool last_use = q < R0 / 2;
-#endif
                 const double x0 = last_use ? buf_load_nt(rx, at, 0) : buf_load(rx, at, 0);
                 const double x1 = last_use ? buf_load_nt(rx, at + 8, 0) : buf_load(rx, at + 8, 0);
                 const double g0 = buf_load(rw, at, 0), g1 = buf_load(rw, at + 8, 0);   // 0 in the padding

@@ -21,10 +21,6 @@
 
 #include "specmix.h"
 
-#ifndef OSZ_SPLIT_ABL      // (timing builds with one phase switched off)
-#define OSZ_SPLIT_ABL 0
-#endif
-
 namespace osz {
 namespace mix {
 
@@ -101,11 +97,7 @@ __global__ __launch_bounds__(NT) void specsplit_kernel(SplitArgs g) {
                 }
             }
 #pragma unroll 4
-#if OSZ_SPLIT_ABL == 4
-            for (int j = jh + t; j < 0; j += NT) {
-#else
             for (int j = jh + t; j < M; j += NT) {
-#endif
                 const unsigned at = 16u * (unsigned)j;
                 const double x0 = buf_load(rx, at, 0), x1 = buf_load(rx, at + 8, 0);
                 sB += x0 + x1;
@@ -157,15 +149,9 @@ __global__ __launch_bounds__(NT) void specsplit_kernel(SplitArgs g) {
             for (int n = 0; n < R0; ++n) {
                 const int j = b + n * S0;
                 const unsigned at = 16u * (unsigned)j;
-#if OSZ_SPLIT_ABL == 3
-                const double x0 = 1.0 + at, x1 = 2.0;
-                double g0, g1;
-                if (at == 12345u) {
-#else
                 const double x0 = buf_load(rx, at, 0), x1 = buf_load(rx, at + 8, 0);
                 double g0, g1;                                                           // 0 in the padding
                 if (wpair) {
-#endif
                     const buf_d2 gg = buf_load2(rw, at, 0);     // (an even window: a point lies inside it or beyond it)
                     g0 = gg[0];
                     g1 = gg[1];
@@ -196,11 +182,7 @@ __global__ __launch_bounds__(NT) void specsplit_kernel(SplitArgs g) {
         asm volatile("" : "+v"(tt));
         // ---- the passes of the two S0-point transforms, in place (specmix.h)
         int B = S0;
-#if OSZ_SPLIT_ABL == 1
-        for (int p = 1; p < 1; ++p) {
-#else
         for (int p = 1; p < a.npass; ++p) {
-#endif
             const int r = a.radix[p];
             const int S = B / r;
             const Split sp = lone ? Split{g.blkfast1[p], g.div1[p], g.inv1[p]} : Split{a.blkfast[p], a.div[p], a.inv[p]};
@@ -222,11 +204,7 @@ __global__ __launch_bounds__(NT) void specsplit_kernel(SplitArgs g) {
         for (int m = 0; m < kAcc / 2; ++m) {
             const int i = tt + NT * m;
             asm volatile("" ::: "memory");   // one pair at a time
-#if OSZ_SPLIT_ABL == 2
-            if (i < 0) {
-#else
             if (i < npairs) {
-#endif
                 int ia, ib, offa = 0, offb, k;
                 if (pair) {
                     ia = i, ib = S0 - 1 - i, offb = S0, k = qa + R0 * i;

@@ -478,9 +478,9 @@ def test_few_channels_take_several_chunks_per_launch(dev):
 @pytest.mark.gpu
 def test_tolerance_knob_reaches_every_table(dev):
     """osz_chain_zp_tolerance: 0 is the default (1e-15); a relaxed cut shortens the zero-phase
-    kernel's lag, and the pair kernels' tables (OSZ_ZP_NEGA=0 builds them through build_zp, which
-    ignored the knob until round 5: ADVICE r4) follow it too -- checked through the lag, which is
-    256 x the left tail's rows for either kernel."""
+    kernel's lag, and the pair kernels' tables (build_zp builds them where the one-block tables are
+    not eligible; it ignored the knob until round 5: ADVICE r4) follow it too -- checked through the
+    lag, which is 256 x the left tail's rows for either kernel."""
     taps = sps.firwin(256, 0.4)
     f0, i0 = dev.FirStream(taps, 1), dev.SosStream(BP, 1)
     try:
