@@ -467,6 +467,34 @@ int osz_magphase(const double *z, int64_t ldz, int nch, int64_t n, double *mag,
 int osz_simpson(const double *p, int64_t ldp, int nch, int64_t a, int64_t m, double dx,
                 double *out, void *stream);
 
+/* ---- phase-locked power (experimental/coupling/estimators.py) -------- */
+/*
+ * PhaseLock.index (reference estimators.py:172-177): out[0, *count) = the
+ * positions i < n, in ascending order, of the 1-D complex chunk z (interleaved
+ * c128, device) whose phase -- numpy.angle mapped to [0, 2 pi), computed as
+ * osz_magphase computes it -- satisfies lo < phase < hi.  out: device int64 of
+ * capacity n; work: device int64 scratch of 2049 elements; *count is written
+ * to HOST memory (the call synchronises `stream`).
+ */
+int osz_phase_index(const double *z, int64_t n, double lo, double hi, int64_t *work,
+                    int64_t *out, int64_t *count, void *stream);
+/*
+ * PhaseLock._avg (estimators.py:200-230) for the real index set and nsur
+ * shifted copies of it in one call, on one chunk: amp (L), device f64, the
+ * Hilbert amplitudes of the chunk; idx (nidx), device int64, the chunk's phase
+ * indices in ascending order.  Set 0 is idx itself; set s in 1..nsur is
+ * (idx + shifts[s - 1]) mod max_shift.  With h = ceil(W/2), a position q of a
+ * set contributes iff h <= q and q + floor(W/2) <= L, and then
+ *   sums[s, k] += sum over those q of amp[q - h + k]^2   (k < W, pitch ldsums)
+ *   counts[s]  += their number                           (device int64)
+ * sums and counts are accumulators the caller zeroes once and carries across
+ * the chunks of a signal.  Fixed summation order, no atomics on sums: two runs
+ * give the same bits.
+ */
+int osz_lock_accumulate(const double *amp, int64_t L, const int64_t *idx, int64_t nidx,
+                        const int64_t *shifts, int nsur, int64_t max_shift, int64_t W,
+                        double *sums, int64_t ldsums, int64_t *counts, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

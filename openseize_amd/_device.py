@@ -1081,3 +1081,42 @@ def checksum(x2d):
                                 x2d.shape[1], ctypes.byref(bits),
                                 ctypes.byref(fsum), stream_ptr()))
     return bits.value, fsum.value
+
+
+def phase_index(z, lo, hi):
+    """osz_phase_index: the ascending int64 positions (CUDA tensor) of the 1-D complex128
+    CUDA tensor z whose phase in [0, 2 pi) satisfies lo < phase < hi."""
+    lib = require_gpu()
+    n = z.numel()
+    work = torch.empty(2049, dtype=torch.int64, device=z.device)
+    full = torch.empty(max(n, 1), dtype=torch.int64, device=z.device)
+    count = ctypes.c_int64()
+    _lib.check(lib.osz_phase_index(ptr(z), n, float(lo), float(hi), ptr(work), ptr(full),
+                                   ctypes.byref(count), stream_ptr()))
+    out = torch.empty(count.value, dtype=torch.int64, device=z.device)
+    if count.value:
+        _lib.check(lib.osz_memcpy_d2d(ptr(out), ptr(full), 8 * count.value, stream_ptr()))
+    return out
+
+
+def zeros(shape, dtype, device="cuda"):
+    """A zero-filled CUDA tensor (osz_memset)."""
+    t = torch.empty(shape, dtype=dtype, device=device)
+    if t.numel():
+        _lib.check(require_gpu().osz_memset(ptr(t), 0, t.numel() * t.element_size(),
+                                            stream_ptr()))
+    return t
+
+
+def lock_accumulate(amp, idx, shifts, max_shift, window, sums, counts):
+    """osz_lock_accumulate: adds one chunk's windowed powers amp^2 around the positions idx
+    (set 0) and around (idx + shifts[s-1]) mod max_shift (set s) to the accumulators
+    sums (S+1, window) float64 and counts (S+1,) int64.  amp: 1-D float64, idx and
+    shifts: 1-D int64, all CUDA tensors; idx ascending."""
+    lib = require_gpu()
+    nsur = shifts.numel()
+    assert sums.shape == (nsur + 1, window) and counts.shape == (nsur + 1,)
+    _lib.check(lib.osz_lock_accumulate(ptr(amp), amp.numel(), ptr(idx), idx.numel(),
+                                       ptr(shifts) if nsur else None, nsur, int(max_shift),
+                                       int(window), ptr(sums), sums.stride(0), ptr(counts),
+                                       stream_ptr()))

@@ -149,6 +149,10 @@ SIGNATURES = {
     "osz_complex_join": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, ctypes.c_int, c_i64, c_vp,
                                         c_i64, c_vp]),
     "osz_magphase": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "osz_phase_index": (ctypes.c_int, [c_vp, c_i64, ctypes.c_double, ctypes.c_double, c_vp, c_vp,
+                                       ctypes.POINTER(c_i64), c_vp]),
+    "osz_lock_accumulate": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_int, c_i64,
+                                           c_i64, c_vp, c_i64, c_vp, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

@@ -142,6 +142,15 @@ __device__ __forceinline__ void buf_store(double v, __amdgpu_buffer_rsrc_t r, un
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(buf_u2, v), r, lane_bytes, row_bytes, 2);
 }
 
+// numpy.angle(z) mapped to [0, 2 pi): the phase of osz_magphase (glue.hip), which
+// osz_phase_index (coupling.hip) recomputes to select exactly the samples whose phase passes
+__device__ __forceinline__ double phase_2pi(double2 v) {
+    constexpr double kTwoPi = 6.283185307179586476925286766559;
+    double p = atan2(v.y, v.x);
+    if (p < 0.0) p += kTwoPi;
+    return p;
+}
+
 // rccl.hip: in-place all-reduce(sum) of `count` float64 / int64 elements over
 // the ranks of an ncclComm_t; RCCL is bound at run time (dlopen)
 int rccl_allreduce_sum(void *buf, size_t count, bool is_f64, void *comm, hipStream_t st);

@@ -181,16 +181,11 @@ __global__ __launch_bounds__(256) void magphase_kernel(const double2 *__restrict
                                                        int64_t n, double *__restrict__ mag,
                                                        double *__restrict__ phase, int64_t ldo) {
     const int c = blockIdx.y;
-    constexpr double kTwoPi = 6.283185307179586476925286766559;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
         const double2 v = z[(int64_t)c * ldz + i];
         if (mag) mag[(int64_t)c * ldo + i] = hypot(v.x, v.y);
-        if (phase) {
-            double p = atan2(v.y, v.x);
-            if (p < 0.0) p += kTwoPi;
-            phase[(int64_t)c * ldo + i] = p;
-        }
+        if (phase) phase[(int64_t)c * ldo + i] = phase_2pi(v);
     }
 }
 

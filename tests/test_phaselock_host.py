@@ -1,0 +1,148 @@
+"""PhaseLock without a GPU: the surrogate shift draws of the reference in both ``ncores``
+modes, the argument errors, and a NumPy restatement of the reference's windowed power
+average (estimators.py:200-230) checked against tests/golden/g21_phaselock.npz.  The GPU
+tests (test_gpu_phaselock.py) hold the device kernels to this restatement."""
+
+import numpy as np
+import pytest
+from scipy import stats
+from scipy.stats import false_discovery_control as fdr
+
+from openseize_amd.experimental.coupling.estimators import PhaseLock
+from openseize_amd.filtering.special import Hilbert
+
+CENTERS = [40, 60, 80]
+# case -> (fs, chunksize, seed of the signal); every case: 30 s, window 1, 25 surrogates
+CASES = {"a_": (500, 7000, 2101), "b_": (333, 7000, 2102), "c_": (500, 40000, 2101)}
+
+
+def signal(fs, seconds, seed):
+    """make_golden_phaselock.signal: 8 Hz phase modulating a 60 Hz amplitude, plus noise."""
+    rng = np.random.default_rng(seed)
+    t = np.arange(int(fs * seconds)) / fs
+    theta = np.sin(2 * np.pi * 8 * t + 0.3)
+    gamma = (1.0 + 0.8 * np.cos(2 * np.pi * 8 * t + 0.3)) * np.sin(2 * np.pi * 60 * t)
+    return 2.0 * theta + 0.7 * gamma + 0.5 * rng.standard_normal(t.size)
+
+
+def split(flat, lengths):
+    return np.split(flat, np.cumsum(lengths)[:-1])
+
+
+def lock_sums(amps, indices, shifts, max_shift, W):
+    """Restatement of osz_lock_accumulate over all chunks: (sums (S+1, W), counts (S+1,)).
+    Set 0 is ``indices``; set s is (indices + shifts[s-1]) % max_shift.  With h = ceil(W/2)
+    a position q of a chunk of length L contributes amps[q - h : q - h + W]**2 iff
+    h <= q and q + W // 2 <= L -- the windows the reference's slicing leaves whole."""
+    h = -(-W // 2)
+    sums = np.zeros((len(shifts) + 1, W))
+    counts = np.zeros(len(shifts) + 1, dtype=np.int64)
+    for s, shift in enumerate([None] + list(shifts)):
+        for amp, idx in zip(amps, indices):
+            q = np.asarray(idx, dtype=np.int64)
+            q = q if shift is None else (q + shift) % max_shift
+            q = q[(q >= h) & (q + W // 2 <= amp.size)]
+            if q.size:
+                sums[s] += (amp[q[:, None] - h + np.arange(W)] ** 2).sum(axis=0)
+            counts[s] += q.size
+    return sums, counts
+
+
+def lock_estimate(sums, counts):
+    """(power, unadjusted p-values) from the accumulators, as the reference's _estimate."""
+    avg = sums / counts[:, None]
+    power, sur = avg[0], avg[1:]
+    z = (power - sur.mean(axis=0)) / (sur.std(axis=0) / np.sqrt(len(sur)))
+    return power, 1 - stats.norm.cdf(z)
+
+
+def reference_shifts(seed, max_shift, surrogates, ncentres, ncores):
+    """The shifts per centre the reference draws: in sequence with one core, the same
+    sequence for every centre with more."""
+    rng = np.random.default_rng(seed)
+    if ncores > 1:
+        one = [rng.integers(0, max_shift) for _ in range(surrogates)]
+        return [one] * ncentres
+    return [[rng.integers(0, max_shift) for _ in range(surrogates)] for _ in range(ncentres)]
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+@pytest.mark.parametrize("ncores", [1, 3])
+def test_restatement_reproduces_reference_powers(golden, case, ncores):
+    g = golden("g21_phaselock.npz")
+    fs, cs, _ = CASES[case]
+    amp = g[f"{case}amp60"]
+    n = amp.size
+    amps = [amp[i:i + cs] for i in range(0, n, cs)]
+    indices = split(g[f"{case}idx"], g[f"{case}idx_len"])
+    shifts = reference_shifts(0, min(cs, n), 25, 3, ncores)[1]      # the 60 Hz centre
+    sums, counts = lock_sums(amps, indices, shifts, min(cs, n), fs * 1)
+    power, p = lock_estimate(sums, counts)
+    ref_pow = g[f"{case}pow{ncores}"][1]
+    np.testing.assert_allclose(power, ref_pow, rtol=0, atol=1e-12 * np.abs(ref_pow).max())
+    np.testing.assert_allclose(fdr(p), g[f"{case}pv{ncores}"][1], rtol=0, atol=1e-9)
+
+
+def test_ncores_modes_differ_in_the_reference(golden):
+    """The fixture shows the reference's two outcomes: the first centre agrees, the others
+    do not; after one core the rng has moved on, after three it has not."""
+    g = golden("g21_phaselock.npz")
+    np.testing.assert_array_equal(g["a_pv1"][0], g["a_pv3"][0])
+    assert np.abs(g["a_pv1"][1:] - g["a_pv3"][1:]).max() > 1e-3
+    fresh = np.random.default_rng(0).integers(0, 2**62)
+    assert g["a_rng3"][0] == fresh and g["a_rng1"][0] != fresh
+    rng = np.random.default_rng(0)
+    for _ in range(3 * 25):
+        rng.integers(0, 7000)
+    assert g["a_rng1"][0] == rng.integers(0, 2**62)
+
+
+def test_shuffle_matches_reference(golden):
+    g = golden("g21_phaselock.npz")
+    est = PhaseLock(Hilbert(width=4, fs=500), chunksize=7000, seed=7)
+    est.indices = split(g["a_idx"], g["a_idx_len"])
+    got = np.concatenate([np.concatenate(est.shuffle(15000)) for _ in range(5)])
+    np.testing.assert_array_equal(got, g["e_shuffle"])
+    # one draw per call
+    rng = np.random.default_rng(7)
+    for _ in range(5):
+        rng.integers(0, 7000)
+    assert est.rng.integers(0, 2**62) == rng.integers(0, 2**62)
+
+
+def test_attributes_and_resets():
+    h = Hilbert(width=4, fs=500)
+    est = PhaseLock(h, chunksize=1000, seed=3)
+    assert est.hilbert is h and est.fs == 500 and est.chunksize == 1000
+    assert est.indices is None
+    assert est.rng.integers(0, 2**62) == np.random.default_rng(3).integers(0, 2**62)
+    for attr, value in (("chunksize", 2000), ("hilbert", Hilbert(width=5, fs=500)),
+                        ("fs", 250)):
+        est.indices = [np.arange(3)]
+        setattr(est, attr, value)
+        assert est.indices is None, attr
+    assert est.fs == 500          # fs follows the Hilbert filter, as in the reference
+
+
+def test_argument_errors():
+    est = PhaseLock(Hilbert(width=4, fs=500), chunksize=7000)
+    est.indices = [np.arange(10, 20)]
+    x = np.zeros(3000)
+    with pytest.raises(TypeError):
+        est.estimate(x, [40], window=0.0033, verbose=False)     # 1.65 samples
+    with pytest.raises(ValueError):
+        est.estimate(x, [40], window=0, verbose=False)
+    with pytest.raises(ValueError):
+        est.estimate(np.zeros((2, 3000)), [40], verbose=False)
+    with pytest.raises(ValueError):
+        est.index(np.zeros((2, 3000)), [6, 10], [4, 12])
+
+
+def test_restatement_validity_edges():
+    """The restatement's validity rule on a hand-sized case: windows at exactly ceil(W/2)
+    and L - W//2 count, one sample further does not; odd W runs from -ceil(W/2)."""
+    W, L = 5, 20
+    amp = np.arange(L, dtype=float)
+    sums, counts = lock_sums([amp], [np.array([2, 3, 18, 19])], [], 1000, W)
+    assert counts[0] == 2                                   # q = 3 and q = 18
+    np.testing.assert_array_equal(sums[0], amp[0:5] ** 2 + amp[15:20] ** 2)
