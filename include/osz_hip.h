@@ -193,6 +193,15 @@ int osz_chain_forward(osz_fir_t fir, osz_sos_t sos, const double *x, int64_t ldx
  * pair's tables on first use (cached on the handles); a handle paired otherwise before
  * gets its own carried state back on `stream`.  Diagnostic: tests and coverage tables. */
 int osz_chain_forward_route(osz_fir_t fir, osz_sos_t sos, void *stream);
+/* The plan behind osz_chain_forward_route, for tests that check every compiled instance
+ * (read-only: it builds the pair's tables as the route does and decides nothing).  Fills
+ * out[0 .. n), n >= 6, with: route (as osz_chain_forward_route), rows (NB on route 2, NR on
+ * routes 1 and 0 -- route 0: the FIR part's rows, 0 when the fused scan cannot run), NM and
+ * NS (modes, slow modes; 0 on route 0, NS 0 on route 1), lane_table (route 0: 1 when the
+ * cascade has the lane tables of chain_kernel<NR, true>, at most 8 sections), has_instance
+ * (1 when the dispatcher finds a compiled kernel for this plan); the rest 0.  0 or an
+ * osz_status_t. */
+int osz_chain_forward_plan(osz_fir_t fir, osz_sos_t sos, void *stream, int32_t *out, int n);
 
 /*
  * One steady-state step of the FIR -> sosfiltfilt chain: osz_chain_forward of the
@@ -285,6 +294,13 @@ int osz_chain_wait(osz_sos_t sos, void *stream);
  *                           samples is not what the continued stream would have there)
  */
 int64_t osz_chain_zp_lag(osz_fir_t fir, osz_sos_t sos);
+/* The zero-phase plan of this pair (read-only, as osz_chain_zp_lag: it builds the tables and
+ * decides nothing), for tests that check every compiled instance.  Fills out[0 .. n), n >= 8,
+ * with: kernel (0 refused, 1 the pair kernel chain_zp_kernel, 2 one block per transform,
+ * chain_zpn_kernel), rows (NR or NB), NM, NS (0 for the pair kernel), R, Rf (burst rows
+ * backwards / forwards), RM (rows the instance holds: 5, 8 or 12), has_instance (1 when the
+ * dispatcher finds a compiled kernel); the rest 0.  0 or an osz_status_t. */
+int osz_chain_zp_plan(osz_fir_t fir, osz_sos_t sos, int32_t *out, int n);
 int osz_chain_zp_tolerance(osz_fir_t fir, osz_sos_t sos, double tol);
 int osz_chain_zp_reach(osz_fir_t fir, osz_sos_t sos, int64_t step);
 int64_t osz_chain_zp_min_chunk(osz_fir_t fir, osz_sos_t sos);

@@ -740,6 +740,14 @@ def chain_forward_route(fir, sos):
     return r
 
 
+def chain_forward_plan(fir, sos):
+    """The plan behind chain_forward_route (C ABI: osz_chain_forward_plan): route, rows, NM, NS,
+    lane_table (route 0: the cascade has chain_kernel's lane tables), has_instance."""
+    out = (ctypes.c_int32 * 6)()
+    _lib.check(fir.lib.osz_chain_forward_plan(fir.h, sos.h, stream_ptr(), out, 6))
+    return dict(zip(("route", "rows", "NM", "NS", "lane_table", "has_instance"), out))
+
+
 def chain_step(fir, sos, x2d, fa, fb=None, f_out=None, y_out=None, defer=False):
     """One steady-state step of FIR -> sosfiltfilt (C ABI: osz_chain_step): the
     fused forward half of chunk ``x2d`` -> f, and beside it, on the SOS
@@ -770,6 +778,14 @@ def chain_zp_lag(fir, sos):
     """Delay of the zero-phase chain kernel in samples, or -1 when this pair of filters
     does not take it (C ABI: osz_chain_zp_lag)."""
     return int(fir.lib.osz_chain_zp_lag(fir.h, sos.h))
+
+
+def chain_zp_plan(fir, sos):
+    """The zero-phase plan of this pair (C ABI: osz_chain_zp_plan): kernel (0 refused, 1 pair,
+    2 one block per transform), rows, NM, NS, R, Rf, RM (rows the instance holds), has_instance."""
+    out = (ctypes.c_int32 * 8)()
+    _lib.check(fir.lib.osz_chain_zp_plan(fir.h, sos.h, out, 8))
+    return dict(zip(("kernel", "rows", "NM", "NS", "R", "Rf", "RM", "has_instance"), out))
 
 
 def chain_zp_min_chunk(fir, sos):

@@ -77,11 +77,13 @@ SIGNATURES = {
                                             c_vp, c_i64, c_vp]),
     "osz_chain_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
     "osz_chain_forward_route": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "osz_chain_forward_plan": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int]),
     "osz_chain_step": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                       c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
                                       ctypes.c_int, c_vp]),
     "osz_chain_wait": (ctypes.c_int, [c_vp, c_vp]),
     "osz_chain_zp_lag": (c_i64, [c_vp, c_vp]),
+    "osz_chain_zp_plan": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int]),
     "osz_chain_zp_tolerance": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double]),
     "osz_chain_zp_reach": (ctypes.c_int, [c_vp, c_vp, c_i64]),
     "osz_chain_zp_min_chunk": (c_i64, [c_vp, c_vp]),

@@ -162,6 +162,23 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(ChainArgs g,
 
 }  // namespace osz
 
+namespace osz {
+// the time-scan instance for rows of nr x 256 and a cascade with (v2) or without a lane table
+using chain_kern_t = void (*)(ChainArgs, const SosSection *);
+static chain_kern_t chain_kernel_pick(int nr, bool v2) {
+    static const chain_kern_t kerns1[8] = {chain_kernel<8, false>,  chain_kernel<9, false>,
+                                           chain_kernel<10, false>, chain_kernel<11, false>,
+                                           chain_kernel<12, false>, chain_kernel<13, false>,
+                                           chain_kernel<14, false>, chain_kernel<15, false>};
+    static const chain_kern_t kerns2[8] = {chain_kernel<8, true>,  chain_kernel<9, true>,
+                                           chain_kernel<10, true>, chain_kernel<11, true>,
+                                           chain_kernel<12, true>, chain_kernel<13, true>,
+                                           chain_kernel<14, true>, chain_kernel<15, true>};
+    if (nr < 8 || nr > 15) return nullptr;
+    return (v2 ? kerns2 : kerns1)[nr - 8];
+}
+}  // namespace osz
+
 using namespace osz;
 
 extern "C" {
@@ -254,23 +271,14 @@ static int chain_forward_impl(osz_fir_t fir, osz_sos_t sos, const double *x, int
             g.npairs = npairs;
             g.nruns = (int)nruns;
             g.pre_pairs = (int)pre;
-            using kern_t = void (*)(ChainArgs, const SosSection *);
-            static const kern_t kerns1[8] = {chain_kernel<8, false>,  chain_kernel<9, false>,
-                                             chain_kernel<10, false>, chain_kernel<11, false>,
-                                             chain_kernel<12, false>, chain_kernel<13, false>,
-                                             chain_kernel<14, false>, chain_kernel<15, false>};
-            static const kern_t kerns2[8] = {chain_kernel<8, true>,  chain_kernel<9, true>,
-                                             chain_kernel<10, true>, chain_kernel<11, true>,
-                                             chain_kernel<12, true>, chain_kernel<13, true>,
-                                             chain_kernel<14, true>, chain_kernel<15, true>};
-            const kern_t *kerns = ltab ? kerns2 : kerns1;
+            const chain_kern_t kern = chain_kernel_pick(nr, ltab != nullptr);
             const size_t lds = sizeof(fft::cube::C2) * fft::cube::SLOTS +
                                sizeof(double) * (2 * 4 * 2 + 2 * kSosMaxSec * 2) +
                                (ltab ? sizeof(double) * (size_t)sos->nsec * 4 * kSos2Tab : 0);
-            OSZ_DYN_LDS(kerns[nr - 8], lds);
+            OSZ_DYN_LDS(kern, lds);
             {
                 KernelTimer kt("chain_fwd", st);
-                hipLaunchKernelGGL(kerns[nr - 8], dim3((unsigned)nruns, fir->nch), dim3(256), lds,
+                hipLaunchKernelGGL(kern, dim3((unsigned)nruns, fir->nch), dim3(256), lds,
                                    st, g, dsec);
             }
             OSZ_HIP(hipGetLastError());
@@ -318,6 +326,33 @@ int osz_chain_forward_route(osz_fir_t fir, osz_sos_t sos, void *stream) {
     int route = 0;
     if (spec_route(fir, sos, as_stream(stream), &route)) return -1;
     return route;
+}
+
+int osz_chain_forward_plan(osz_fir_t fir, osz_sos_t sos, void *stream, int32_t *out, int n) {
+    OSZ_REQUIRE(fir && sos && out && n >= 6 && fir->nch == sos->nch,
+                "osz_chain_forward_plan: null argument, channel counts differ or n=%d < 6", n);
+    const int route = osz_chain_forward_route(fir, sos, stream);
+    if (route < 0) return OSZ_ERR_STATE;          // (the message is osz_chain_forward_route's)
+    for (int i = 0; i < n; ++i) out[i] = 0;
+    out[0] = route;
+    if (route == 0) {
+        // the fused time scan (chain_forward_impl): one FIR part of rows of 256 samples
+        if (fir->parts.size() != 1 || fir->ntaps < 2) return OSZ_OK;
+        const int nr = fir->parts[0].step / 256;
+        const bool v2 = sos->nsec <= kSos2MaxSec;      // (sos_lane_table_for)
+        out[1] = nr;
+        out[4] = v2;
+        out[5] = chain_kernel_pick(nr, v2) != nullptr;
+        return OSZ_OK;
+    }
+    int rt = 0, rows = 0, nm = 0, ns = 0, has = 0;
+    int rc = spec_plan(fir, sos, as_stream(stream), &rt, &rows, &nm, &ns, &has);
+    if (rc) return rc;
+    out[1] = rows;
+    out[2] = nm;
+    out[3] = ns;
+    out[5] = has;
+    return OSZ_OK;
 }
 
 // Do two (nch, n) views, rows ld apart, share an element?  Views of one parent

@@ -687,12 +687,33 @@ static int spec_link(osz_fir_s *fir, osz_sos_s *sos, hipStream_t st, ChainSpec *
     return OSZ_OK;
 }
 
+// the pair kernel's instance for this link (null: none compiled)
+static spec_kern_t spec_kernel_pick(const ChainSpec *s) {
+    if (s->NR < 8 || s->NR > 15) return nullptr;
+    return s->NM == 2 ? spec_kernel_for<2, 16>(s->NR) : s->NM == 4 ? spec_kernel_for<4, 16>(s->NR)
+           : s->NM == 6 ? spec_kernel_for<6, 16>(s->NR) : nullptr;
+}
+
 // which kernel osz_chain_forward runs whole blocks of this pair on (osz_chain_forward_route)
 int spec_route(osz_fir_s *fir, osz_sos_s *sos, hipStream_t st, int *route) {
     ChainSpec *s = nullptr;
     int rc = spec_link(fir, sos, st, &s);
     if (rc) return rc;
     *route = !s->eligible ? 0 : s->nega ? 2 : 1;
+    return OSZ_OK;
+}
+
+// ... and its plan on routes 1 and 2 (osz_chain_forward_plan): rows, modes, slow modes, whether
+// an instance exists
+int spec_plan(osz_fir_s *fir, osz_sos_s *sos, hipStream_t st, int *route, int *rows, int *nm, int *ns,
+              int *has) {
+    int rc = spec_route(fir, sos, st, route);
+    if (rc || *route == 0) return rc;
+    const ChainSpec *s = sos->spec;
+    *rows = s->NR;
+    *nm = s->NM;
+    *ns = s->nega ? s->NS : 0;
+    *has = (s->nega ? zpn_fwd_kernel_for(s->NR, s->NM, s->NS) != nullptr : spec_kernel_pick(s) != nullptr);
     return OSZ_OK;
 }
 
@@ -772,8 +793,8 @@ int spec_try_forward(osz_fir_s *fir, osz_sos_s *sos, const double *x, int64_t ld
     s->since_import += n;
     // the composite spectrum is requested per pair (FirPair HPRE = 16): resident in registers
     // (HPRE = -1) the kernel spills 36 of its 64 words and the step takes 2.54 instead of 2.29 ms
-    spec_kern_t kern = s->NM == 2 ? spec_kernel_for<2, 16>(NR) : s->NM == 4 ? spec_kernel_for<4, 16>(NR)
-                                                                            : spec_kernel_for<6, 16>(NR);
+    spec_kern_t kern = spec_kernel_pick(s);
+    if (!kern) return fail(OSZ_ERR_STATE, "forward pair kernel: no instance for %d rows, %d modes", NR, s->NM);
     const size_t lds = sizeof(fft::cube::C2) * fft::cube::SLOTS +
                        sizeof(double) * (2 * kSpecFit + 2 * 2 * s->NM * 2 + 5 * kSpecRMax * s->NM * 2 +
                                          kSpecRMax * s->NM * 2 + 32 * s->NM * 2 + 2 * s->NM * kSpecFit);

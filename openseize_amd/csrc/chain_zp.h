@@ -91,6 +91,7 @@ __device__ __forceinline__ bool zp_exact_nanpos(const double *xb, int count, int
 // chain_zpn_*.hip: the kernel for NB rows per block (20 .. 30), NM modes (2, 4, 6, 8) of which the
 // first NS (2, 4, 6) are slow
 using zp_kern_t = void (*)(ZpArgs);
+using spec::zpn_rm_for;   // (spec_tables.h: the burst rows of the instance for nb, r)
 zp_kern_t zpn_kernel_for(int nb, int nm, int ns, int r);
 // ... and its forward-chain instances (FIR -> sosfilt, no left tail; chain_spec.hip launches them)
 zp_kern_t zpn_fwd_kernel_for(int nb, int nm, int ns);

@@ -701,6 +701,13 @@ static zp_kern_t zp_kernel_for(int nr) {
                                    chain_zp_kernel<14, NM, DMA>, chain_zp_kernel<15, NM, DMA>};
     return k[nr - 8];
 }
+// the instance a chunk of this pair of handles runs on (null: none compiled)
+static zp_kern_t zp_kernel_pick(const ChainZp *s) {
+    if (s->nega) return zpn_kernel_for(s->NR, s->NM, s->NS, s->R);
+    if (s->NR < 8 || s->NR > 15) return nullptr;
+    return s->NM == 2 ? zp_kernel_for<2, true>(s->NR) : s->NM == 4 ? zp_kernel_for<4, true>(s->NR)
+           : s->NM == 6 ? zp_kernel_for<6, true>(s->NR) : nullptr;     // (rows by LDS-DMA, as the one-block kernel's)
+}
 // one chunk through the kernel; hist: keep the input a later osz_chain_zp_finish replays
 static int zp_launch(ChainZp *s, const double *x, int64_t ldx, int64_t n, double *y0, int64_t ldy0,
                      int64_t n0, double *y, int64_t ldy, hipStream_t st) {
@@ -767,10 +774,7 @@ static int zp_launch(ChainZp *s, const double *x, int64_t ldx, int64_t n, double
         g.hist = nullptr;
         g.hist_len = 0;
     }
-    zp_kern_t kern = s->nega    ? zpn_kernel_for(NR, s->NM, s->NS, s->R)
-                     : s->NM == 2 ? zp_kernel_for<2, true>(NR)
-                     : s->NM == 4 ? zp_kernel_for<4, true>(NR)
-                                  : zp_kernel_for<6, true>(NR);     // (rows by LDS-DMA, as the one-block kernel's)
+    zp_kern_t kern = zp_kernel_pick(s);
     if (!kern) return fail(OSZ_ERR_STATE, "zero-phase kernel: no instance for %d rows, %d modes (%d slow)", NR, s->NM, s->NS);
     const size_t lds = zp_lds_bytes(s);
     OSZ_DYN_LDS(kern, lds);
@@ -795,6 +799,24 @@ int64_t osz_chain_zp_lag(osz_fir_t fir, osz_sos_t sos) {
     ChainZp *s = nullptr;
     if (zp_get(fir, sos, &s) != OSZ_OK || !s->eligible) return -1;
     return 256 * (int64_t)s->R;
+}
+
+int osz_chain_zp_plan(osz_fir_t fir, osz_sos_t sos, int32_t *out, int n) {
+    OSZ_REQUIRE(fir && sos && out && n >= 8, "osz_chain_zp_plan: null argument or n=%d < 8", n);
+    ChainZp *s = nullptr;
+    int rc = zp_get(fir, sos, &s);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) out[i] = 0;
+    if (!s->eligible) return OSZ_OK;
+    out[0] = s->nega ? 2 : 1;
+    out[1] = s->NR;
+    out[2] = s->NM;
+    out[3] = s->NS;
+    out[4] = s->R;
+    out[5] = s->Rf;
+    out[6] = s->nega ? zpn_rm_for(s->NR, s->R) : kSpecRMax;
+    out[7] = zp_kernel_pick(s) != nullptr;
+    return OSZ_OK;
 }
 
 int osz_chain_zp_tolerance(osz_fir_t fir, osz_sos_t sos, double tol) {

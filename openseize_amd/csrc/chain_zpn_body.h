@@ -482,9 +482,12 @@ static zp_kern_t zpn_kernel_nb(int nb, int r) {
                                     chain_zpn_kernel<26, NM, NS, 8>};
     static const zp_kern_t k12[4] = {chain_zpn_kernel<20, NM, NS, 12>, chain_zpn_kernel<21, NM, NS, 12>,
                                      chain_zpn_kernel<22, NM, NS, 12>, chain_zpn_kernel<23, NM, NS, 12>};
-    if (nb < 24) return r <= 12 ? k12[nb - 20] : nullptr;
-    if (r > kSpecRMax) return nb <= 26 && r <= 8 ? k8[nb - 24] : nullptr;
-    return k[nb - 24];
+    switch (zpn_rm_for(nb, r)) {   // (spec_tables.h)
+    case 12: return k12[nb - 20];
+    case 8: return k8[nb - 24];
+    case kSpecRMax: return k[nb - 24];
+    default: return nullptr;
+    }
 }
 
 #define OSZ_ZPN_CAT2(a, b) a##b

@@ -33,6 +33,14 @@ typedef long double ld_t;
 constexpr int kFit = 64;      // samples of row 15 the fit reads (one wave)
 constexpr int kRMax = 5;      // burst rows supported (the pair kernels)
 constexpr int kRMaxN = 12;    // ... by the one-block kernel (chain_zpn_body.h: its instances hold 5, 8 or 12 rows)
+// burst rows RM of the one-block instance that holds a left tail of r rows in blocks of nb rows
+// (0: none; chain_zpn_body.h dispatches on it): more than five rows only in blocks of 24 ... 26
+// rows (R <= 32 - NB), more than eight in 20 ... 23
+inline int zpn_rm_for(int nb, int r) {
+    if (nb < 24) return r <= kRMaxN ? kRMaxN : 0;
+    if (r > kRMax) return nb <= 26 && r <= 8 ? 8 : 0;
+    return kRMax;
+}
 // Where a burst is cut off, relative to the norm of the composite impulse response.  What is cut
 // is an error proportional to the INPUT's magnitude (a block's ringing is driven by everything in
 // it, offsets included, and only cancels between neighbouring blocks as far as both were kept):
@@ -592,8 +600,11 @@ inline TablesZp build_zpn(const double *taps, int wlen, const double *sos, int n
             if (!rb && sqrtl(left2[il]) <= tail_tol * tot) rb = r;
         }
         // (the right tail: five rows at most, and its second landing place, rows D .. D + rf - 1,
-        // inside the window's lower half, which the kernel's forward bursts address)
-        if (rb && rf && rf <= rb && rf <= kRMax && rb <= D && D + rf <= cand && D + rf <= 16) {
+        // inside the window's lower half, which the kernel's forward bursts address; the held rows,
+        // the block's last rb, below the D + rf rows the previous block's tail and right burst add
+        // to: a run starts one block early, and that block has no previous block -- held rows
+        // above row D + rf - 1 came out short by what they missed)
+        if (rb && rf && rf <= rb && rf <= kRMax && rb <= D && rb + rf <= cand - D && D + rf <= 16) {
             NB = cand;
             R = rb;
             Rf = rf;

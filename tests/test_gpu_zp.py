@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import scipy.signal as sps
 
+from chain_cells import run_stream, whole_stream_reference  # noqa: F401 (benchmarks/dc_probe.py reads them here)
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-9
@@ -26,49 +28,6 @@ def dev():
     _lib.load()
     from openseize_amd import _device
     return _device
-
-
-def whole_stream_reference(xh, h, sos):
-    """Forward pass from sosfilt_zi * u[0], backward pass over everything (zero-extended)."""
-    total = xh.shape[1]
-    u = sps.oaconvolve(xh, h[None], axes=-1)[:, :total]
-    zi = sps.sosfilt_zi(sos)[:, None, :] * u[:, :1][None]
-    f, _ = sps.sosfilt(sos, u, axis=-1, zi=zi)
-    ext = np.concatenate([f, np.zeros((xh.shape[0], 8192))], 1)
-    return sps.sosfilt(sos, ext[:, ::-1], axis=-1)[:, ::-1][:, :total]
-
-
-def run_stream(dev, x, h, sos, lens, split=False):
-    """The chunks of x through osz_chain_zp_step; returns (outputs as one tensor whose
-    column q is stream sample q - lag, lag).  split: the outputs of every step go to the
-    tail of the previous chunk's buffer and the head of the current one, as a caller that
-    cuts the stream into chunks of its own has them."""
-    import torch
-    C = x.shape[0]
-    fir, iir = dev.FirStream(h, C), dev.SosStream(sos, C)
-    try:
-        lag = dev.chain_zp_lag(fir, iir)
-        assert lag >= 0
-        iir.set_state_scaled((x[:, :1] * float(h[0])).contiguous(), 0)
-        dev.chain_zp_open(fir, iir, 0)
-        outs, o = [], 0
-        if not split:
-            for n in lens:
-                outs.append(dev.chain_zp_step(fir, iir, x[:, o:o + n]))
-                o += n
-            return torch.cat(outs, 1), lag
-        cut = lag + 37                                        # where the caller's chunks begin
-        bufs = [torch.full((C, cut), float("nan"), dtype=torch.float64, device="cuda")]
-        for n in lens:
-            bufs.append(torch.full((C, n), float("nan"), dtype=torch.float64, device="cuda"))
-        for k, n in enumerate(lens):
-            prev, cur = bufs[k], bufs[k + 1]
-            dev.chain_zp_step(fir, iir, x[:, o:o + n], out=cur[:, :n - cut], tail=prev[:, prev.shape[1] - cut:])
-            o += n
-        return torch.cat([b[:, :b.shape[1]] for b in bufs], 1)[:, :sum(lens)], lag
-    finally:
-        fir.close()
-        iir.close()
 
 
 CASES = [
