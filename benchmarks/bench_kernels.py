@@ -27,7 +27,113 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps
 
 
+def edf_lines(out):
+    """The EDF decode and encode kernels on one geometry, and the end-to-end write of that block
+    against the host route (``--edf`` runs these lines alone)."""
+    import shutil
+    import tempfile
+    import torch
+    from openseize_amd import _device as dev
+    from openseize_amd import _lib
+    # EDF record decode on the device (SURVEY 8f rank 3): 64 channels x 1000
+    # samples per 1 s record, 4000 records of little-endian int16 already in
+    # HBM -> (64, 4e6) float64: 2 B read + 8 B written per sample
+    nch_e, spr_e, nrec_e = 64, 1000, 4000
+    raw = torch.randint(-2000, 2000, (nrec_e * nch_e * spr_e,), dtype=torch.int16, device="cuda")
+    as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    choff = as_dev((np.arange(nch_e) * spr_e).astype(np.int32))
+    spr = as_dev(np.full(nch_e, spr_e, np.int32))
+    lens = as_dev(np.full(nch_e, spr_e * nrec_e, np.int64))
+    slope, offs = as_dev(np.full(nch_e, 0.25)), as_dev(np.full(nch_e, -3.0))
+    width = spr_e * nrec_e
+    dec = torch.empty((nch_e, width), dtype=torch.float64, device="cuda")
+    lib = _lib.load()
+
+    def edf():
+        _lib.check(lib.osz_edf_decode(dev.ptr(raw), nch_e * spr_e, nch_e, dev.ptr(choff), dev.ptr(spr),
+                                      dev.ptr(slope), dev.ptr(offs), dev.ptr(lens), 0, 0, width,
+                                      ctypes.c_double(float("nan")), dev.ptr(dec), dec.stride(0),
+                                      dev.stream_ptr()))
+    dt = timed(edf, 5)
+    out.append({"workload": "EDF decode 64 ch x 4e6 samples (int16 records in HBM -> f64)",
+                "ms_per_chunk": dt * 1e3, "Msamples_s": nch_e * width / dt / 1e6,
+                "algorithmic_GBps": 10 * nch_e * width / dt / 1e9})
+
+
+    # EDF record encode, the same geometry the other way round: (64, 4e6) float64 resident ->
+    # 4000 records of little-endian int16 in HBM: 8 B read + 2 B written per sample
+    xe = dev.synth_normal(nch_e, width, seed=5) * 500.0
+    enc = torch.empty(nrec_e * nch_e * spr_e, dtype=torch.int16, device="cuda")
+    counter = torch.zeros(2, dtype=torch.int64, device="cuda")
+    dt = timed(lambda: dev.edf_encode(xe, spr, choff, slope, offs, nch_e * spr_e, nrec_e, enc, counter), 5)
+    out.append({"workload": "EDF encode 64 ch x 4e6 samples (f64 in HBM -> int16 records)",
+                "ms_per_chunk": dt * 1e3, "Msamples_s": nch_e * width / dt / 1e6,
+                "algorithmic_GBps": 10 * nch_e * width / dt / 1e9,
+                "roofline_frac_of_8TBps": 10 * nch_e * width / dt / 8e12})
+
+    # the same block to a file on a memory-backed directory: Writer.write (encode on the device,
+    # int16 over PCIe) against the route without it (float64 over PCIe, NumPy per record group,
+    # tofile), alternating, five times each
+    from openseize_amd.file_io import edf as edf_io
+    hdr = {"version": "0", "patient": "bench", "recording": "bench", "start_date": "01.01.26",
+           "start_time": "00.00.00", "header_bytes": 256 + 256 * nch_e, "reserved_0": "",
+           "num_records": nrec_e, "record_duration": 1.0, "num_signals": nch_e,
+           "names": [f"ch{i}" for i in range(nch_e)], "transducers": [""] * nch_e,
+           "physical_dim": ["uV"] * nch_e, "physical_min": [-8192.0] * nch_e,
+           "physical_max": [8191.75] * nch_e, "digital_min": [-32768.0] * nch_e,
+           "digital_max": [32767.0] * nch_e, "prefiltering": [""] * nch_e,
+           "samples_per_record": [spr_e] * nch_e, "reserved_1": [""] * nch_e}
+    chans = list(range(nch_e))
+    plan = edf_io.record_plan(hdr, chans)
+    head = edf_io.header_bytes(edf_io.Header.from_dict(hdr).filter(chans))
+    shm = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
+    tmp = tempfile.mkdtemp(prefix="osz_edf_", dir=shm)
+
+    def device_route(path):
+        with edf_io.Writer(path) as writer:
+            writer.write(hdr, xe, chans, verbose=False)
+
+    def host_route(path):
+        xh = xe.cpu().numpy()
+        s_, o_ = plan["slope"][:, None], plan["offset"][:, None]
+        with open(path, "wb") as fp:
+            fp.write(head)
+            for r0 in range(0, nrec_e, plan["group"]):
+                r1 = min(r0 + plan["group"], nrec_e)
+                d = np.rint((xh[:, r0 * spr_e:r1 * spr_e] - o_) / s_).astype("<i2")
+                d.reshape(nch_e, r1 - r0, spr_e).transpose(1, 0, 2).tofile(fp)
+
+    try:
+        pa, pb = os.path.join(tmp, "device.edf"), os.path.join(tmp, "host.edf")
+        device_route(pa)
+        host_route(pb)
+        same = open(pa, "rb").read() == open(pb, "rb").read()
+        times = {"device": [], "host": []}
+        for _ in range(5):
+            for label, route, path in (("device", device_route, pa), ("host", host_route, pb)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                route(path)
+                times[label].append(time.perf_counter() - t0)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    nbytes = 2 * nch_e * width
+    out.append({"workload": "EDF write 64 ch x 4e6 samples resident -> file (memory-backed directory): "
+                            "Writer.write against .cpu().numpy() + NumPy rint + tofile, alternating",
+                "memory_backed": shm is not None, "files_identical": same,
+                "writer_median_s": float(np.median(times["device"])),
+                "host_route_median_s": float(np.median(times["host"])),
+                "writer_s": times["device"], "host_route_s": times["host"],
+                "writer_file_GBps": nbytes / float(np.median(times["device"])) / 1e9})
+
+
 def main():
+    if "--edf" in sys.argv:
+        out = []
+        edf_lines(out)
+        for o in out:
+            print(json.dumps(o))
+        return
     import scipy.signal as sps
     import torch
     from openseize_amd import _device as dev
@@ -170,29 +276,7 @@ def main():
     out.append({"workload": "d2d copy 256 ch x 2^20 (practical HBM ceiling)",
                 "ms_per_chunk": dt * 1e3, "algorithmic_GBps": 16 * CH * N / dt / 1e9})
 
-    # EDF record decode on the device: 64 channels x 1000
-    # samples per 1 s record, 4000 records of little-endian int16 already in
-    # HBM -> (64, 4e6) float64: 2 B read + 8 B written per sample
-    nch_e, spr_e, nrec_e = 64, 1000, 4000
-    raw = torch.randint(-2000, 2000, (nrec_e * nch_e * spr_e,), dtype=torch.int16, device="cuda")
-    as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    choff = as_dev((np.arange(nch_e) * spr_e).astype(np.int32))
-    spr = as_dev(np.full(nch_e, spr_e, np.int32))
-    lens = as_dev(np.full(nch_e, spr_e * nrec_e, np.int64))
-    slope, offs = as_dev(np.full(nch_e, 0.25)), as_dev(np.full(nch_e, -3.0))
-    width = spr_e * nrec_e
-    dec = torch.empty((nch_e, width), dtype=torch.float64, device="cuda")
-    lib = _lib.load()
-
-    def edf():
-        _lib.check(lib.osz_edf_decode(dev.ptr(raw), nch_e * spr_e, nch_e, dev.ptr(choff), dev.ptr(spr),
-                                      dev.ptr(slope), dev.ptr(offs), dev.ptr(lens), 0, 0, width,
-                                      ctypes.c_double(float("nan")), dev.ptr(dec), dec.stride(0),
-                                      dev.stream_ptr()))
-    dt = timed(edf, 5)
-    out.append({"workload": "EDF decode 64 ch x 4e6 samples (int16 records in HBM -> f64)",
-                "ms_per_chunk": dt * 1e3, "Msamples_s": nch_e * width / dt / 1e6,
-                "algorithmic_GBps": 10 * nch_e * width / dt / 1e9})
+    edf_lines(out)
 
     # transfer-function filter through the public API, device-resident:
     # Notch (order 2, one section) zero-phase on 64 ch x 2^20

@@ -527,6 +527,27 @@ int osz_edf_decode(const int16_t *raw, int reclen, int nch, const int32_t *choff
                    const int64_t *len, int64_t rec0, int64_t start, int64_t width,
                    double padvalue, double *out, int64_t ldo, void *stream);
 
+/* ---- EDF record encode ------------------------------------------------- */
+/*
+ * The inverse of osz_edf_decode, for edf.Writer (reference file_io/edf.py:660-697
+ * _records, _encipher): physical float64 samples -> the little-endian int16 data
+ * records of an EDF file.  Row c of the source is the first h[c] columns of `carry`
+ * (nch rows of pitch ldc, nc columns; null: none) followed by the nx columns of x
+ * (nch rows of pitch ldx).  Per-channel device arrays spr / choff (int32: samples per
+ * record, offset inside an output record; reclen = sum of spr) and slope / offset
+ * (f64).  out: device int16, nrec * reclen values, 8-byte aligned; record r holds for
+ * each channel in turn rint((row_c[r spr[c] + j] - offset[c]) / slope[c]), j < spr[c]:
+ * one IEEE subtraction, one IEEE division, round half to even.  Results above 32767
+ * (and +inf) write 32767, below -32768 (and -inf) -32768, NaN writes 0 -- where the
+ * reference's cast is undefined -- and counter[0] (saturated) and counter[1] (NaN),
+ * two device uint64 the caller zeroes, are added to.  A sample neither source holds
+ * reads as NaN.  10 bytes of HBM traffic per sample.
+ */
+int osz_edf_encode(const double *x, int64_t ldx, int64_t nx, const double *carry, int64_t ldc,
+                   int64_t nc, const int32_t *h, int nch, const int32_t *spr, const int32_t *choff,
+                   const double *slope, const double *offset, int reclen, int64_t nrec,
+                   int16_t *out, uint64_t *counter, void *stream);
+
 /* ---- synthetic device-resident source (benchmarks, tests) ------------- */
 /* x[c, j] = N(0,1) keyed by (seed, ch0 + c, n0 + j): counter-based, so any
  * shard or chunk is reproducible on CPU and GPU alike. */

@@ -1079,6 +1079,30 @@ def take(x2d, idx):
     return y
 
 
+def edf_encode(x2d, spr, choff, slope, offset, reclen, nrec, out, counter, carry=None, h=None):
+    """osz_edf_encode: ``nrec`` EDF records of int16 into the 1-D int16 CUDA tensor ``out``.
+    Row c of the source is ``carry[c, :h[c]]`` followed by ``x2d[c]`` (float64 CUDA tensors with
+    unit column stride; ``x2d`` may be None when the carry holds everything).  spr / choff: int32,
+    slope / offset: float64, h: int32 CUDA tensors of one entry per row; counter: two int64 the
+    kernel adds its saturated and NaN counts to."""
+    lib = require_gpu()
+    nch = spr.numel()
+    for t in (x2d, carry):
+        if t is not None and (t.dim() != 2 or t.shape[0] != nch or t.dtype != torch.float64
+                              or (t.shape[1] > 1 and t.stride(1) != 1)):
+            raise ValueError(f"edf_encode: source {tuple(t.shape)} is not float64 ({nch}, n) rows")
+    if out.dtype != torch.int16 or out.numel() < nrec * reclen or not out.is_contiguous():
+        raise ValueError("edf_encode: out holds fewer than nrec * reclen int16 values")
+    nx = 0 if x2d is None else x2d.shape[1]
+    _lib.check(lib.osz_edf_encode(
+        ptr(x2d) if nx else None, x2d.stride(0) if nx else 0, nx,
+        ptr(carry) if carry is not None else None, carry.stride(0) if carry is not None else 0,
+        carry.shape[1] if carry is not None else 0, ptr(h) if carry is not None else None,
+        nch, ptr(spr), ptr(choff), ptr(slope), ptr(offset), int(reclen), int(nrec), ptr(out),
+        ptr(counter), stream_ptr()))
+    return out
+
+
 def synth_normal(nch, n, seed=0, ch0=0, n0=0, out=None, device="cuda"):
     """Device-resident synthetic float64 N(0,1) block keyed by
     (seed, channel, sample) -- osz_synth_normal."""
