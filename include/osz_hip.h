@@ -511,6 +511,28 @@ int osz_lock_accumulate(const double *amp, int64_t L, const int64_t *idx, int64_
                         const int64_t *shifts, int nsur, int64_t max_shift, int64_t W,
                         double *sums, int64_t ldsums, int64_t *counts, void *stream);
 
+/* ---- Welch cross-spectra over all channel pairs (spectra/estimators.py csd, coherence) -- */
+/*
+ * X: the (nseg, nch, nfreq) interleaved c128 block an OSZ_SPEC_DFT_SEGMENTS push wrote
+ * (device); acc: (nch, nch, nfreq) c128 raw sums (device), owned and zeroed by the caller and
+ * carried across the pushes of a stream:
+ *   acc[i, j, f] += sum over s of conj(X[s, i, f]) X[s, j, f]        for i <= j
+ * summed segment by segment from the stored value, so the sums do not depend on where the
+ * stream is cut; no atomics: two runs give the same bits.  Entries with i > j are not touched.
+ */
+int osz_cross_accumulate(const void *X, int64_t nseg, int nch, int nfreq, void *acc, void *stream);
+typedef enum {
+    OSZ_CROSS_SPECTRUM = 0,    /* out: (nch, nch, nfreq) c128                 */
+    OSZ_CROSS_COHERENCE = 1    /* out: (nch, nch, nfreq) f64                  */
+} osz_cross_mode;
+/*
+ * Spectrum: out[i, j] = acc[i, j] / count, every bin but DC (and the last one when
+ * nfft_is_even) doubled; out[j, i] = conj(out[i, j]); the imaginary part of out[i, i] is 0.
+ * `out` may be `acc`.  Coherence: out[i, j] = out[j, i] = |acc[i, j]|^2 / (Re acc[i, i] Re acc[j, j]).
+ */
+int osz_cross_finish(const void *acc, int64_t count, int nch, int nfreq, int nfft_is_even, int mode,
+                     void *out, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

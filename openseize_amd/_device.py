@@ -1160,3 +1160,28 @@ def lock_accumulate(amp, idx, shifts, max_shift, window, sums, counts):
                                        ptr(shifts) if nsur else None, nsur, int(max_shift),
                                        int(window), ptr(sums), sums.stride(0), ptr(counts),
                                        stream_ptr()))
+
+
+def cross_accumulate(X, acc):
+    """osz_cross_accumulate: acc[i, j, f] += sum_s conj(X[s, i, f]) X[s, j, f] for i <= j.
+    X: (nseg, nch, nfreq), acc: (nch, nch, nfreq), contiguous complex128 CUDA tensors."""
+    lib = require_gpu()
+    nseg, nch, nfreq = X.shape
+    if (X.dtype != torch.complex128 or acc.dtype != torch.complex128 or tuple(acc.shape) != (nch, nch, nfreq)
+            or not X.is_contiguous() or not acc.is_contiguous()):
+        raise ValueError(f"cross_accumulate: X {tuple(X.shape)} / acc {tuple(acc.shape)} are not contiguous "
+                         "complex128 (nseg, nch, nfreq) / (nch, nch, nfreq)")
+    _lib.check(lib.osz_cross_accumulate(ptr(X), nseg, nch, nfreq, ptr(acc), stream_ptr()))
+
+
+def cross_finish(acc, count, nfft, mode):
+    """osz_cross_finish on the raw sums ``acc`` (nch, nch, nfreq) of ``count`` segments.
+    CROSS_SPECTRUM: the one-sided mean cross-spectra, written over ``acc`` and returned;
+    CROSS_COHERENCE: a new float64 tensor of the same shape."""
+    lib = require_gpu()
+    nch, _, nfreq = acc.shape
+    out = acc if mode == _lib.CROSS_SPECTRUM else torch.empty(tuple(acc.shape), dtype=torch.float64,
+                                                              device=acc.device)
+    _lib.check(lib.osz_cross_finish(ptr(acc), int(count), nch, nfreq, int(nfft % 2 == 0), mode, ptr(out),
+                                    stream_ptr()))
+    return out

@@ -24,6 +24,7 @@ SPEC_PSD_MEAN, SPEC_PSD_SEGMENTS, SPEC_DFT_SEGMENTS = 0, 1, 2
 EW_ADD, EW_MUL, EW_DIV, EW_STANDARDIZE = 0, 1, 2, 3
 BCAST_SCALAR, BCAST_ROW, BCAST_COL, BCAST_FULL = 0, 1, 2, 3
 DETREND = {"constant": 0, "linear": 1}
+CROSS_SPECTRUM, CROSS_COHERENCE = 0, 1
 
 
 class OszLibraryError(RuntimeError):
@@ -155,6 +156,9 @@ SIGNATURES = {
                                        ctypes.POINTER(c_i64), c_vp]),
     "osz_lock_accumulate": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_int, c_i64,
                                            c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "osz_cross_accumulate": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "osz_cross_finish": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, c_vp, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),
