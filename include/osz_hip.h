@@ -511,6 +511,44 @@ int osz_lock_accumulate(const double *amp, int64_t L, const int64_t *idx, int64_
                         const int64_t *shifts, int nsur, int64_t max_shift, int64_t W,
                         double *sums, int64_t ldsums, int64_t *counts, void *stream);
 
+/* ---- phase-amplitude comodulogram (experimental/coupling/estimators.py ModulationIndex) -- */
+/*
+ * z: `rows` rows of n interleaved c128 samples, pitch ldz in complex elements (device).
+ * bins[r, i] (device uint8, pitch ldb) = min(nbins - 1, floor(phase * nbins / (2 pi))) with the
+ * phase in [0, 2 pi) computed as osz_magphase computes it; a NaN phase gives 255: the sample
+ * belongs to no bin.  2 <= nbins <= 64.
+ */
+int osz_phase_bins(const double *z, int rows, int64_t n, int64_t ldz, int nbins, uint8_t *bins,
+                   int64_t ldb, void *stream);
+/*
+ * One chunk of length L of the Tort et al. (2010) amplitude-by-phase sums, for the real pairing
+ * (set 0) and nsur time-shifted copies of the amplitudes (set s, shifted by sigma_s =
+ * shifts[s - 1] mod L; sigma_0 = 0), all (p, a, s) in one launch.  bins: (np, L) uint8 of
+ * osz_phase_bins, pitch ldb; amp: (na, L) f64, pitch lda; shifts: nsur int64 (all device).
+ *   sums[p, a, s, b] += sum over i with bins[p, i] = b of amp[a, (i + sigma_s) mod L]
+ *   counts[p, b]     += #{i : bins[p, i] = b}
+ * sums: contiguous (np, na, nsur + 1, nbins) f64, counts: (np, nbins) int64, accumulators the
+ * caller zeroes once and carries across the chunks of a signal.  Codes >= nbins (255) are
+ * skipped; a non-finite amplitude propagates into the sums it falls into; L = 0 is a no-op.
+ * Every sum is owned by one wave and added in a fixed order, no atomics on sums: two runs give
+ * the same bits.
+ */
+int osz_pac_accumulate(const uint8_t *bins, int np, int64_t ldb, const double *amp, int na,
+                       int64_t lda, int64_t L, const int64_t *shifts, int nsur, int nbins,
+                       double *sums, int64_t *counts, void *stream);
+/*
+ * The modulation index of every (p, a, set): with m_b = sums / counts and P_b = m_b / sum m,
+ *   mi[p, a, s] = 1 + sum_b P_b ln P_b / ln nbins        (0 ln 0 = 0)
+ *   dist[p, a, :] = P of set 0
+ * mi: (np, na, nsets) f64, dist: (np, na, nbins) f64 (device).  A phase row with an empty bin
+ * gives NaN for that whole row.  The index is summed as
+ * sum_b (P_b ln(nbins P_b) - P_b + 1 / nbins) / ln nbins, the same number as sum P = 1, with
+ * terms that are all >= 0 and second order in the rounding of sum P, so that an index of 1e-4
+ * keeps its digits.
+ */
+int osz_pac_finish(const double *sums, const int64_t *counts, int np, int na, int nsets, int nbins,
+                   double *mi, double *dist, void *stream);
+
 /* ---- Welch cross-spectra over all channel pairs (spectra/estimators.py csd, coherence) -- */
 /*
  * X: the (nseg, nch, nfreq) interleaved c128 block an OSZ_SPEC_DFT_SEGMENTS push wrote

@@ -1046,12 +1046,20 @@ def complex_join(re2d, im2d):
     return z
 
 
-def magphase(z2d, want_mag=True, want_phase=True):
+def magphase(z2d, want_mag=True, want_phase=True, mag_out=None):
     """(|z|, angle(z) in [0, 2 pi)) of a complex128 CUDA tensor (nch, n)
-    (osz_magphase); an output that is not wanted is None."""
+    (osz_magphase); an output that is not wanted is None.  ``mag_out``: a contiguous
+    float64 CUDA tensor of z2d's shape that receives |z| instead of a new one."""
     lib = require_gpu()
     shape = tuple(z2d.shape)
-    mag = torch.empty(shape, dtype=torch.float64, device=z2d.device) if want_mag else None
+    if mag_out is not None and (tuple(mag_out.shape) != shape or mag_out.dtype != torch.float64
+                                or not mag_out.is_contiguous() or mag_out.device != z2d.device):
+        raise ValueError(f"magphase: mag_out {tuple(mag_out.shape)} is not contiguous float64 {shape} "
+                         "on z2d's device")
+    mag = None
+    if want_mag:
+        mag = mag_out if mag_out is not None else torch.empty(shape, dtype=torch.float64,
+                                                              device=z2d.device)
     ph = torch.empty(shape, dtype=torch.float64, device=z2d.device) if want_phase else None
     _lib.check(lib.osz_magphase(ptr(z2d), z2d.stride(0), shape[0], shape[1],
                                 ptr(mag) if want_mag else None, ptr(ph) if want_phase else None,
@@ -1160,6 +1168,60 @@ def lock_accumulate(amp, idx, shifts, max_shift, window, sums, counts):
                                        ptr(shifts) if nsur else None, nsur, int(max_shift),
                                        int(window), ptr(sums), sums.stride(0), ptr(counts),
                                        stream_ptr()))
+
+
+def phase_bins(z2d, nbins, out=None):
+    """osz_phase_bins: the phase-bin code of every sample of the (rows, n) complex128 CUDA
+    tensor z2d, a uint8 CUDA tensor of the same shape: min(nbins - 1, floor(phase * nbins /
+    2 pi)) with osz_magphase's phase, 255 where the phase is NaN.  ``out``: a contiguous
+    uint8 CUDA tensor of that shape to write into."""
+    lib = require_gpu()
+    rows, n = z2d.shape
+    if z2d.dtype != torch.complex128 or (n > 1 and z2d.stride(1) != 1):
+        raise ValueError(f"phase_bins: z {tuple(z2d.shape)} is not complex128 rows")
+    if out is not None and (tuple(out.shape) != (rows, n) or out.dtype != torch.uint8
+                            or not out.is_contiguous()):
+        raise ValueError(f"phase_bins: out {tuple(out.shape)} is not contiguous uint8 {(rows, n)}")
+    bins = out if out is not None else torch.empty((rows, n), dtype=torch.uint8, device=z2d.device)
+    _lib.check(lib.osz_phase_bins(ptr(z2d), rows, n, max(z2d.stride(0), n), int(nbins), ptr(bins),
+                                  max(n, 1), stream_ptr()))
+    return bins
+
+
+def pac_accumulate(bins, amp, shifts, nbins, sums, counts):
+    """osz_pac_accumulate: adds one chunk to the accumulators sums (P, A, S + 1, nbins) float64
+    and counts (P, nbins) int64 (contiguous): sums[p, a, s, b] += the amplitudes amp[a, (i +
+    shifts[s-1] mod L) mod L] of the samples i with bins[p, i] = b (set 0: no shift).  bins:
+    (P, L) uint8, amp: (A, L) float64, shifts: (S,) int64, all CUDA tensors."""
+    lib = require_gpu()
+    (np_, L), (na, La), nsur = bins.shape, amp.shape, shifts.numel()
+    if (bins.dtype != torch.uint8 or amp.dtype != torch.float64 or La != L
+            or (L > 1 and (bins.stride(1) != 1 or amp.stride(1) != 1))):
+        raise ValueError(f"pac_accumulate: bins {tuple(bins.shape)} / amp {tuple(amp.shape)} are not "
+                         "uint8 (P, L) / float64 (A, L) rows")
+    if (tuple(sums.shape) != (np_, na, nsur + 1, nbins) or tuple(counts.shape) != (np_, nbins)
+            or sums.dtype != torch.float64 or counts.dtype != torch.int64
+            or not sums.is_contiguous() or not counts.is_contiguous()):
+        raise ValueError(f"pac_accumulate: sums {tuple(sums.shape)} / counts {tuple(counts.shape)} are not "
+                         f"contiguous float64 ({np_}, {na}, {nsur + 1}, {nbins}) / int64 ({np_}, {nbins})")
+    if shifts.dtype != torch.int64 or shifts.ndim != 1 or not shifts.is_contiguous() or not shifts.is_cuda:
+        raise ValueError(f"pac_accumulate: shifts {tuple(shifts.shape)} {shifts.dtype} are not a contiguous "
+                         "int64 (S,) CUDA tensor")
+    _lib.check(lib.osz_pac_accumulate(ptr(bins), np_, max(bins.stride(0), L), ptr(amp), na,
+                                      max(amp.stride(0), L), L, ptr(shifts) if nsur else None, nsur,
+                                      int(nbins), ptr(sums), ptr(counts), stream_ptr()))
+
+
+def pac_finish(sums, counts):
+    """osz_pac_finish: (mi (P, A, S + 1), dist (P, A, nbins)) float64 CUDA tensors from the
+    accumulators of pac_accumulate."""
+    lib = require_gpu()
+    np_, na, nsets, nbins = sums.shape
+    mi = torch.empty((np_, na, nsets), dtype=torch.float64, device=sums.device)
+    dist = torch.empty((np_, na, nbins), dtype=torch.float64, device=sums.device)
+    _lib.check(lib.osz_pac_finish(ptr(sums), ptr(counts), np_, na, nsets, nbins, ptr(mi), ptr(dist),
+                                  stream_ptr()))
+    return mi, dist
 
 
 def cross_accumulate(X, acc):

@@ -156,6 +156,13 @@ SIGNATURES = {
                                        ctypes.POINTER(c_i64), c_vp]),
     "osz_lock_accumulate": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_int, c_i64,
                                            c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "osz_phase_bins": (ctypes.c_int, [c_vp, ctypes.c_int, c_i64, c_i64, ctypes.c_int, c_vp, c_i64,
+                                      c_vp]),
+    "osz_pac_accumulate": (ctypes.c_int, [c_vp, ctypes.c_int, c_i64, c_vp, ctypes.c_int, c_i64,
+                                          c_i64, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                          c_vp]),
+    "osz_pac_finish": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, c_vp, c_vp, c_vp]),
     "osz_cross_accumulate": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "osz_cross_finish": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, c_vp, c_vp]),
