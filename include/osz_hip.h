@@ -571,6 +571,41 @@ typedef enum {
 int osz_cross_finish(const void *acc, int64_t count, int nch, int nfreq, int nfft_is_even, int mode,
                      void *out, void *stream);
 
+/* ---- phase-based connectivity over all channel pairs (spectra/estimators.py phase_connectivity) -- */
+/*
+ * X as for osz_cross_accumulate; lag: four (nch, nch, nfreq) f64 planes (device), owned and
+ * zeroed by the caller and carried across the pushes of a stream.  With
+ * d = Im(conj(X[s, i, f]) X[s, j, f]) = fma(Re X_i, Im X_j, -(Im X_i Re X_j)), for i <= j:
+ *   lag[0, i, j, f] += sum over s of d          lag[1, i, j, f] += sum over s of |d|
+ *   lag[2, i, j, f] += sum over s of d^2        lag[3, i, j, f] += sum over s of sign(d)
+ * sign(+-0) = 0 and sign(NaN) = NaN.  Summed segment by segment from the stored value, no
+ * atomics: the sums do not depend on where the stream is cut and two runs give the same bits.
+ * Entries with i > j are not touched.
+ */
+int osz_lag_accumulate(const void *X, int64_t nseg, int nch, int nfreq, double *lag, void *stream);
+/*
+ * X[k] <- X[k] / |X[k]| for the n interleaved c128 values at X (device), in place; 0 gives NaN.
+ * osz_cross_accumulate on the result adds z / |z| of every pair, z = conj(X_i) X_j.
+ */
+int osz_unit_phasors(void *X, int64_t n, void *stream);
+typedef enum {
+    OSZ_PHASE_IMCOH = 0,   /* Im acc[i, j] / sqrt(Re acc[i, i] Re acc[j, j])      reads acc  */
+    OSZ_PHASE_PLV = 1,     /* |accn[i, j]| / count                                 reads accn */
+    OSZ_PHASE_PLI = 2,     /* |lag[3]| / count                                     reads lag  */
+    OSZ_PHASE_WPLI = 3,    /* |lag[0]| / lag[1]                                    reads lag  */
+    OSZ_PHASE_DWPLI = 4    /* (lag[0]^2 - lag[2]) / (lag[1]^2 - lag[2])            reads lag  */
+} osz_phase_mode;
+/*
+ * out (nch, nch, nfreq) f64 from the sums of `count` segments: acc the sums of
+ * osz_cross_accumulate, accn those of the spectra osz_unit_phasors normalised, lag those of
+ * osz_lag_accumulate; the ones `mode` does not read may be null.  out[j, i] = out[i, j], for
+ * imcoh -out[i, j].  In this order: where the diagonal sums of channel i or j are NaN the entry
+ * is NaN; the diagonal is 1.0 for plv and 0.0 for the others; at bin 0, and at the last bin
+ * when nfft_is_even, every measure but plv is 0.0 (and its mirror 0.0); elsewhere 0 / 0 is NaN.
+ */
+int osz_phase_finish(int mode, const void *acc, const void *accn, const double *lag, int64_t count,
+                     int nch, int nfreq, int nfft_is_even, double *out, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

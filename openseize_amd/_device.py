@@ -1247,3 +1247,42 @@ def cross_finish(acc, count, nfft, mode):
     _lib.check(lib.osz_cross_finish(ptr(acc), int(count), nch, nfreq, int(nfft % 2 == 0), mode, ptr(out),
                                     stream_ptr()))
     return out
+
+
+def lag_accumulate(X, lag):
+    """osz_lag_accumulate: with d = Im(conj(X[s, i, f]) X[s, j, f]), lag[0 .. 3, i, j, f] += the
+    sums over s of d, |d|, d^2 and sign(d) for i <= j.  X: (nseg, nch, nfreq) complex128, lag:
+    (4, nch, nch, nfreq) float64, contiguous CUDA tensors."""
+    lib = require_gpu()
+    nseg, nch, nfreq = X.shape
+    if (X.dtype != torch.complex128 or lag.dtype != torch.float64 or tuple(lag.shape) != (4, nch, nch, nfreq)
+            or not X.is_contiguous() or not lag.is_contiguous()):
+        raise ValueError(f"lag_accumulate: X {tuple(X.shape)} / lag {tuple(lag.shape)} are not contiguous "
+                         "complex128 (nseg, nch, nfreq) / float64 (4, nch, nch, nfreq)")
+    _lib.check(lib.osz_lag_accumulate(ptr(X), nseg, nch, nfreq, ptr(lag), stream_ptr()))
+
+
+def unit_phasors(X):
+    """osz_unit_phasors: X <- X / |X| in place on a contiguous complex128 CUDA tensor (0 -> NaN)."""
+    lib = require_gpu()
+    if X.dtype != torch.complex128 or not X.is_contiguous():
+        raise ValueError(f"unit_phasors: X {tuple(X.shape)} {X.dtype} is not contiguous complex128")
+    _lib.check(lib.osz_unit_phasors(ptr(X), X.numel(), stream_ptr()))
+    return X
+
+
+def phase_finish(method, count, nfft, acc=None, accn=None, lag=None):
+    """osz_phase_finish: the float64 (nch, nch, nfreq) measure ``method`` (a key of
+    _lib.PHASE_MODE) from the sums of ``count`` segments: ``acc`` (cross_accumulate of the
+    spectra) for imcoh, ``accn`` (of the unit phasors) for plv, ``lag`` (lag_accumulate) for
+    pli / wpli / dwpli."""
+    lib = require_gpu()
+    sums = {"imcoh": acc, "plv": accn}.get(method, lag)
+    if sums is None:
+        raise ValueError(f"phase_finish: the sums that {method!r} reads were not given")
+    nch, nfreq = sums.shape[-2:]
+    out = torch.empty((nch, nch, nfreq), dtype=torch.float64, device=sums.device)
+    _lib.check(lib.osz_phase_finish(_lib.PHASE_MODE[method], *(ptr(t) if t is not None else None
+                                                               for t in (acc, accn, lag)),
+                                    int(count), nch, nfreq, int(nfft % 2 == 0), ptr(out), stream_ptr()))
+    return out

@@ -25,6 +25,7 @@ EW_ADD, EW_MUL, EW_DIV, EW_STANDARDIZE = 0, 1, 2, 3
 BCAST_SCALAR, BCAST_ROW, BCAST_COL, BCAST_FULL = 0, 1, 2, 3
 DETREND = {"constant": 0, "linear": 1}
 CROSS_SPECTRUM, CROSS_COHERENCE = 0, 1
+PHASE_MODE = {"imcoh": 0, "plv": 1, "pli": 2, "wpli": 3, "dwpli": 4}
 
 
 class OszLibraryError(RuntimeError):
@@ -166,6 +167,10 @@ SIGNATURES = {
     "osz_cross_accumulate": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "osz_cross_finish": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, c_vp, c_vp]),
+    "osz_lag_accumulate": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "osz_unit_phasors": (ctypes.c_int, [c_vp, c_i64, c_vp]),
+    "osz_phase_finish": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_vp, c_i64, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

@@ -1,4 +1,4 @@
-"""psd / stft / csd / coherence: user API over the windowed-DFT path.
+"""psd / stft / csd / coherence / phase_connectivity: user API over the windowed-DFT path.
 
 Same signatures and return values as reference spectra/estimators.py:59-156
 (``psd`` -> (cnt, freqs, mean PSD)) and :160-284 (``stft`` -> (freqs, time,
@@ -7,7 +7,8 @@ accumulates the periodogram sum (K6) and the mean is taken once at the end --
 mathematically the running mean of estimators.py:149-152.  ``csd`` and
 ``coherence`` have no counterpart in the reference: they are ``psd``'s Welch
 average taken over every PAIR of channels (K10), with ``scipy.signal.csd`` /
-``scipy.signal.coherence`` as the yardstick.
+``scipy.signal.coherence`` as the yardstick.  ``phase_connectivity`` (K11) takes the
+phase-based measures (imcoh, plv, pli, wpli, dwpli) from the same segments.
 """
 
 import numpy as np
@@ -92,9 +93,13 @@ def psd(data, fs, axis=-1, resolution=0.5, window="hann", overlap=0.5,
 _CROSS_PUSH_BYTES = 1 << 30
 
 
-def _cross_sums(data, fs, axis, resolution, window, overlap, detrend, scaling):
-    """-> (cnt, freqs, raw sums (C, C, nfreq) complex128 on the device [i <= j filled], nfft,
-    host): the Welch loop ``csd`` and ``coherence`` share."""
+def _cross_stream(data, fs, axis, resolution, window, overlap, detrend, scaling, begin, arrays=1):
+    """The Welch loop over all channel pairs that ``csd``, ``coherence`` and
+    ``phase_connectivity`` share.  Checks the arguments (touching neither the stream nor the
+    device), then calls ``begin(nch, nfreq)`` once -- it allocates the sums and returns the
+    function every push's (nseg, nch, nfreq) complex128 spectra are handed to, which may
+    overwrite them.  ``arrays``: how many complex128 (C, C, nfreq) arrays' worth of host memory
+    the result takes.  -> (cnt, freqs, nfft, host)."""
     pro, nfft, freqs, stride, coeffs, scale, axis_n, layout = _welch_plan(
         data, fs, axis, resolution, window, overlap, scaling)
     if len(pro.shape) == 1:
@@ -110,14 +115,14 @@ def _cross_sums(data, fs, axis, resolution, window, overlap, detrend, scaling):
                          f"than nfft = int(fs / resolution) = {nfft}")
     nch, nfreq = layout.nch, nfft // 2 + 1
     if dev.origin_is_host(pro):
-        _host_result_fits(nch, nfreq)            # (before any work is done for it)
+        _host_result_fits(nch, nfreq, arrays)    # (before any work is done for it)
     dev.require_gpu()
     spec = dev.SpecStream(nfft, nfft, stride, coeffs, scale, detrend, _lib.SPEC_DFT_SEGMENTS, nch)
     feed = _Feed(pro, axis_n, layout)
     cap = max(1, _CROSS_PUSH_BYTES // (16 * nch * nfreq)) * stride
     cnt = 0
     try:
-        acc = dev.zeros((nch, nch, nfreq), dev.torch.complex128)
+        each = begin(nch, nfreq)
         for x2d in feed:
             for at in range(0, x2d.shape[1], cap):
                 X = spec.push(x2d[:, at:at + cap])         # (nseg, nch, nfreq), the handle keeps the tail
@@ -126,21 +131,38 @@ def _cross_sums(data, fs, axis, resolution, window, overlap, detrend, scaling):
                 if nm._linear_trend_refuses(X, detrend) is not None:
                     # (a least-squares trend refuses non-finite data: core/numerical.py:691)
                     raise ValueError(nm._REFUSED)
-                dev.cross_accumulate(X, acc)
+                each(X)
                 cnt += X.shape[0]
     finally:
         spec.close()
     if cnt == 0:
         raise ValueError(f"no complete segment: the stream ended before nfft = int(fs / resolution) = {nfft} "
                          "samples")
-    return cnt, freqs, acc, nfft, feed.host
+    if feed.host:
+        _host_result_fits(nch, nfreq, arrays)
+    return cnt, freqs, nfft, feed.host
 
 
-def _host_result_fits(nch, nfreq):
+def _cross_sums(data, fs, axis, resolution, window, overlap, detrend, scaling):
+    """-> (cnt, freqs, raw sums (C, C, nfreq) complex128 on the device [i <= j filled], nfft,
+    host): what ``csd`` and ``coherence`` take from the loop."""
+    sums = []
+
+    def begin(nch, nfreq):
+        acc = dev.zeros((nch, nch, nfreq), dev.torch.complex128)
+        sums.append(acc)
+        return lambda X: dev.cross_accumulate(X, acc)
+
+    cnt, freqs, nfft, host = _cross_stream(data, fs, axis, resolution, window, overlap, detrend,
+                                           scaling, begin)
+    return cnt, freqs, sums[0], nfft, host
+
+
+def _host_result_fits(nch, nfreq, arrays=1):
     shape = (nch, nch, nfreq)
-    if not assignable(shape, dtype=complex, msg=False):
-        raise MemoryError(f"the {shape} complex128 result needs {16 * nch * nch * nfreq / 1e9:.2f} GB of host "
-                          "memory, more than is available: select fewer channels or lower the resolution")
+    if not assignable((arrays,) + shape, dtype=complex, msg=False):
+        raise MemoryError(f"the {shape} complex128 result needs {arrays * 16 * nch * nch * nfreq / 1e9:.2f} GB of "
+                          "host memory, more than is available: select fewer channels or lower the resolution")
 
 
 def csd(data, fs, axis=-1, resolution=0.5, window="hann", overlap=0.5,
@@ -167,8 +189,6 @@ def csd(data, fs, axis=-1, resolution=0.5, window="hann", overlap=0.5,
     """
     cnt, freqs, acc, nfft, host = _cross_sums(data, fs, axis, resolution, window, overlap,
                                               detrend, scaling)
-    if host:
-        _host_result_fits(acc.shape[0], acc.shape[2])
     S = dev.cross_finish(acc, cnt, nfft, _lib.CROSS_SPECTRUM)
     return cnt, freqs, S.cpu().numpy() if host else S
 
@@ -181,10 +201,94 @@ def coherence(data, fs, axis=-1, resolution=0.5, window="hann", overlap=0.5,
     auto-spectrum is 0 is NaN, as it is in SciPy."""
     cnt, freqs, acc, nfft, host = _cross_sums(data, fs, axis, resolution, window, overlap,
                                               detrend, "density")
-    if host:
-        _host_result_fits(acc.shape[0], acc.shape[2])
     C = dev.cross_finish(acc, cnt, nfft, _lib.CROSS_COHERENCE)
     return cnt, freqs, C.cpu().numpy() if host else C
+
+
+PHASE_METHODS = tuple(_lib.PHASE_MODE)        # ("imcoh", "plv", "pli", "wpli", "dwpli")
+
+
+def _phase_methods(method):
+    names = (method,) if isinstance(method, str) or not isinstance(method, (tuple, list)) else tuple(method)
+    bad = [m for m in names if not isinstance(m, str) or m not in PHASE_METHODS]
+    if bad or not names:
+        raise ValueError(f"unknown phase connectivity method(s) {bad}: choose from {PHASE_METHODS}")
+    return names
+
+
+def phase_connectivity(data, fs, method="wpli", axis=-1, resolution=0.5, window="hann",
+                       overlap=0.5, detrend="constant"):
+    """Phase-based connectivity over all channel pairs, from the Welch segments of ``csd``.
+
+    ``data``, the segment cutting and the argument errors are those of ``csd`` (nfft = int(fs /
+    resolution), stride = nfft - int(nfft * overlap), a trailing partial segment dropped;
+    two-dimensional data, samples along ``axis``).  ``method`` is one name or a tuple of names;
+    with X[s, c, f] the segment spectra, z_s = conj(X_i) X_j, d_s = Im z_s and N = cnt:
+
+    ``"imcoh"``  Im(sum z_s) / sqrt(sum |X_i|^2 sum |X_j|^2), the imaginary part of coherency
+                 (Nolte et al. 2004); antisymmetric, M[j, i] = -M[i, j];
+    ``"plv"``    |sum z_s / |z_s|| / N, the phase-locking value in its spectral form (Lachaux et
+                 al. 1999);
+    ``"pli"``    |sum sign(d_s)| / N, the phase-lag index (Stam et al. 2007);
+    ``"wpli"``   |sum d_s| / sum |d_s|, the weighted phase-lag index (Vinck et al. 2011);
+    ``"dwpli"``  ((sum d_s)^2 - sum d_s^2) / ((sum |d_s|)^2 - sum d_s^2), its debiased square.
+
+    Returns ``(cnt, freqs, M)``: for one name M is float64 (C, C, nfreq) whatever ``axis`` was,
+    for a tuple a dict of name -> such an array, every measure from ONE pass over the stream and
+    bit-identical to the single-name call.  Host data gives ndarrays, CUDA data CUDA tensors.
+    All but imcoh are symmetric, bit for bit; imcoh's mirror is the negated value.
+
+    Fixed points, written and not computed: the diagonal is 1.0 for plv and 0.0 for the others;
+    at f = 0, and at the Nyquist bin when nfft is even, the spectra are real, and imcoh, pli,
+    wpli and dwpli are 0.0 there (both mirrors +0.0).  ``plv`` at f = 0 is NOT fixed: under
+    detrending X[s, c, 0] is what rounding left of a removed mean, and plv there is the phase
+    of rounding noise (a channel whose X is exactly 0 in a segment gives NaN, 0 / 0).  NaN
+    overrides the fixed points: where a channel's own sums are NaN, its row and column are.
+    Elsewhere a zero denominator gives NaN, as IEEE does.
+
+    With ``detrend="constant"`` a non-finite sample in channel k makes row and column k NaN and
+    leaves every other pair as it is without it; ``detrend="linear"`` raises ``ValueError`` then.
+
+    Device memory: per (pair, bin) 16 B of complex sums for imcoh, 16 B for plv (the sums of the
+    unit phasors X / |X|, since z / |z| = conj(X_i / |X_i|) X_j / |X_j|) and 32 B for pli, wpli
+    and dwpli together (sum d, sum |d|, sum d^2, sum sign d) -- only what the requested methods
+    need, up to 64 B per (pair, bin) with everything requested -- plus 8 B per returned measure
+    and per push the segment spectra ``csd`` documents (about 1 GiB at most).  Every sum is added
+    in segment order: the estimate does not depend on how the stream is cut into chunks, and two
+    calls give the same bits.
+    """
+    names = _phase_methods(method)
+    need_acc, need_plv = "imcoh" in names, "plv" in names
+    need_lag = any(m in names for m in ("pli", "wpli", "dwpli"))
+    sums = {}
+
+    def begin(nch, nfreq):
+        if need_acc:
+            sums["acc"] = dev.zeros((nch, nch, nfreq), dev.torch.complex128)
+        if need_plv:
+            sums["accn"] = dev.zeros((nch, nch, nfreq), dev.torch.complex128)
+        if need_lag:
+            sums["lag"] = dev.zeros((4, nch, nch, nfreq), dev.torch.float64)
+
+        def each(X):
+            if need_lag:
+                dev.lag_accumulate(X, sums["lag"])
+            if need_acc:
+                dev.cross_accumulate(X, sums["acc"])
+            if need_plv:
+                # last: the normalisation overwrites the push's spectra
+                dev.cross_accumulate(dev.unit_phasors(X), sums["accn"])
+        return each
+
+    # (float64 results: two of them take one complex128 array's worth of host memory)
+    cnt, freqs, nfft, host = _cross_stream(data, fs, axis, resolution, window, overlap, detrend,
+                                           "density", begin, arrays=(len(set(names)) + 1) // 2)
+    out = {}
+    for m in names:
+        if m not in out:
+            M = dev.phase_finish(m, cnt, nfft, **sums)
+            out[m] = M.cpu().numpy() if host else M
+    return cnt, freqs, out[names[0]] if isinstance(method, str) else out
 
 
 def stft(data, fs, axis=-1, resolution=0.5, window="hann", overlap=0.5,
