@@ -606,6 +606,46 @@ typedef enum {
 int osz_phase_finish(int mode, const void *acc, const void *accn, const double *lag, int64_t count,
                      int nch, int nfreq, int nfft_is_even, double *out, void *stream);
 
+/* ---- delete-one jackknife over the Welch segments (spectra/estimators.py jackknife) ------ */
+typedef enum {             /* theta without segment s, from the totals minus its contribution  */
+    OSZ_JACK_COHERENCE = 0, /* |A - z|^2 / ((P_i - p_i)(P_j - p_j))               reads acc  */
+    OSZ_JACK_IMCOH = 1,     /* Im(A - z) / sqrt((P_i - p_i)(P_j - p_j))           reads acc  */
+    OSZ_JACK_PLV = 2,       /* |U - u| / (count - 1)                              reads accn */
+    OSZ_JACK_PLI = 3,       /* |G - sign d| / (count - 1)                         reads lag  */
+    OSZ_JACK_WPLI = 4,      /* |D - d| / (B - |d|)                                reads lag  */
+    OSZ_JACK_DWPLI = 5      /* ((D - d)^2 - (Q - d^2)) / ((B - |d|)^2 - (Q - d^2)) reads lag  */
+} osz_jack_mode;
+/*
+ * The second pass.  X: (nseg, nch, nfreq) c128 segment spectra (device) as for
+ * osz_cross_accumulate -- for OSZ_JACK_PLV the spectra osz_unit_phasors normalised; acc / accn /
+ * lag: the FINISHED totals of all `count` >= 2 segments of the stream (osz_cross_accumulate of the
+ * spectra, of the unit phasors, osz_lag_accumulate), the ones `mode` does not read may be null.
+ * With z = conj(X_i) X_j of segment s, d = Im z (the expression of osz_lag_accumulate),
+ * p_i = |X_i|^2, A = acc[i, j], P_i = Re acc[i, i], U = accn[i, j], (D, B, Q, G) = lag[0 .. 3]:
+ * theta_(s) as the table says, theta the same expression with nothing taken away, and for i <= j
+ *   dev2[0, i, j, f] += sum over s of (theta_(s) - theta)
+ *   dev2[1, i, j, f] += sum over s of (theta_(s) - theta)^2
+ * dev2: two (nch, nch, nfreq) f64 planes (device), owned and zeroed by the caller and carried
+ * across the pushes; one such array per mode.  Summed segment by segment from the stored value,
+ * no atomics: the sums do not depend on where the stream is cut and two runs give the same bits.
+ * Entries with i > j are not touched.  A zero denominator gives inf or NaN, as IEEE does; with
+ * count = 2 dwpli's theta_(s) is 0 / 0 by definition and is written as NaN.
+ */
+int osz_jackknife_accumulate(int mode, const void *X, int64_t nseg, int nch, int nfreq, const void *acc,
+                             const void *accn, const double *lag, int64_t count, double *dev2, void *stream);
+/*
+ * out (nch, nch, nfreq) f64, out[j, i] = out[i, j] =
+ *   sqrt((count - 1) / count v),  v = dev2[1] - dev2[0]^2 / count         (a NaN stays one)
+ * with v taken as 0 where it does not exceed 4 count 2^-53 dev2[1], the rounding the subtraction
+ * itself may carry (which covers v < 0): the deviations are then equal to within rounding -- with
+ * two segments, coherence, plv, pli and wpli of the one segment left are 1 whichever is left out.
+ * In this order: where the diagonal totals of channel i or j (of the array `mode` reads) are NaN
+ * the entry is NaN; the diagonal is 0.0; at bin 0, and at the last bin when nfft_is_even, every
+ * measure but plv is 0.0.
+ */
+int osz_jackknife_finish(int mode, const double *dev2, const void *acc, const void *accn, const double *lag,
+                         int64_t count, int nch, int nfreq, int nfft_is_even, double *out, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

@@ -1286,3 +1286,55 @@ def phase_finish(method, count, nfft, acc=None, accn=None, lag=None):
                                                                for t in (acc, accn, lag)),
                                     int(count), nch, nfreq, int(nfft % 2 == 0), ptr(out), stream_ptr()))
     return out
+
+
+def _jackknife_totals(who, method, acc, accn, lag, nch, nfreq):
+    """The totals ``method`` (a key of _lib.JACK_MODE) reads, checked: ``acc`` for coherence and
+    imcoh, ``accn`` for plv, ``lag`` for pli / wpli / dwpli."""
+    if method not in _lib.JACK_MODE:
+        raise ValueError(f"{who}: unknown method {method!r}: choose from {tuple(_lib.JACK_MODE)}")
+    on_lag = method in ("pli", "wpli", "dwpli")
+    sums = lag if on_lag else accn if method == "plv" else acc
+    if sums is None:
+        raise ValueError(f"{who}: the totals that {method!r} reads were not given")
+    want = ((4, nch, nch, nfreq), torch.float64) if on_lag else ((nch, nch, nfreq), torch.complex128)
+    if (tuple(sums.shape), sums.dtype) != want or not sums.is_contiguous():
+        raise ValueError(f"{who}: the totals of {method!r}, {tuple(sums.shape)} {sums.dtype}, are not "
+                         f"contiguous {want[1]} {want[0]}")
+    return sums
+
+
+def jackknife_accumulate(method, X, count, dev2, acc=None, accn=None, lag=None):
+    """osz_jackknife_accumulate: with theta_(s) the measure ``method`` without segment s (from
+    the finished totals of all ``count`` segments minus segment s's contribution) and theta the
+    measure itself, dev2[0, i, j, f] += sum_s (theta_(s) - theta) and dev2[1, i, j, f] += the sum
+    of its square, for i <= j.  X: (nseg, nch, nfreq) complex128 (for plv: after unit_phasors),
+    dev2: (2, nch, nch, nfreq) float64, contiguous CUDA tensors; the totals as for phase_finish,
+    plus ``acc`` for coherence."""
+    lib = require_gpu()
+    nseg, nch, nfreq = X.shape
+    if (X.dtype != torch.complex128 or dev2.dtype != torch.float64 or tuple(dev2.shape) != (2, nch, nch, nfreq)
+            or not X.is_contiguous() or not dev2.is_contiguous()):
+        raise ValueError(f"jackknife_accumulate: X {tuple(X.shape)} / dev2 {tuple(dev2.shape)} are not contiguous "
+                         "complex128 (nseg, nch, nfreq) / float64 (2, nch, nch, nfreq)")
+    _jackknife_totals("jackknife_accumulate", method, acc, accn, lag, nch, nfreq)
+    _lib.check(lib.osz_jackknife_accumulate(_lib.JACK_MODE[method], ptr(X), nseg, nch, nfreq,
+                                            *(ptr(t) if t is not None else None for t in (acc, accn, lag)),
+                                            int(count), ptr(dev2), stream_ptr()))
+
+
+def jackknife_finish(method, dev2, count, nfft, acc=None, accn=None, lag=None):
+    """osz_jackknife_finish: the float64 (nch, nch, nfreq) jackknife standard error of ``method``
+    from the sums ``dev2`` of jackknife_accumulate over all ``count`` segments; the totals say
+    where a channel is NaN."""
+    lib = require_gpu()
+    if dev2.ndim != 4 or dev2.shape[0] != 2 or dev2.dtype != torch.float64 or not dev2.is_contiguous():
+        raise ValueError(f"jackknife_finish: dev2 {tuple(dev2.shape)} {dev2.dtype} is not contiguous float64 "
+                         "(2, nch, nch, nfreq)")
+    nch, nfreq = dev2.shape[-2:]
+    _jackknife_totals("jackknife_finish", method, acc, accn, lag, nch, nfreq)
+    out = torch.empty((nch, nch, nfreq), dtype=torch.float64, device=dev2.device)
+    _lib.check(lib.osz_jackknife_finish(_lib.JACK_MODE[method], ptr(dev2),
+                                        *(ptr(t) if t is not None else None for t in (acc, accn, lag)),
+                                        int(count), nch, nfreq, int(nfft % 2 == 0), ptr(out), stream_ptr()))
+    return out

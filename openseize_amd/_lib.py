@@ -26,6 +26,7 @@ BCAST_SCALAR, BCAST_ROW, BCAST_COL, BCAST_FULL = 0, 1, 2, 3
 DETREND = {"constant": 0, "linear": 1}
 CROSS_SPECTRUM, CROSS_COHERENCE = 0, 1
 PHASE_MODE = {"imcoh": 0, "plv": 1, "pli": 2, "wpli": 3, "dwpli": 4}
+JACK_MODE = {"coherence": 0, "imcoh": 1, "plv": 2, "pli": 3, "wpli": 4, "dwpli": 5}
 
 
 class OszLibraryError(RuntimeError):
@@ -171,6 +172,10 @@ SIGNATURES = {
     "osz_unit_phasors": (ctypes.c_int, [c_vp, c_i64, c_vp]),
     "osz_phase_finish": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_vp, c_i64, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "osz_jackknife_accumulate": (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, ctypes.c_int, ctypes.c_int,
+                                                c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "osz_jackknife_finish": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

@@ -8,7 +8,8 @@ mathematically the running mean of estimators.py:149-152.  ``csd`` and
 ``coherence`` have no counterpart in the reference: they are ``psd``'s Welch
 average taken over every PAIR of channels (K10), with ``scipy.signal.csd`` /
 ``scipy.signal.coherence`` as the yardstick.  ``phase_connectivity`` (K11) takes the
-phase-based measures (imcoh, plv, pli, wpli, dwpli) from the same segments.
+phase-based measures (imcoh, plv, pli, wpli, dwpli) from the same segments, and ``jackknife``
+(K12) gives coherence and those five their delete-one standard errors in a second pass.
 """
 
 import numpy as np
@@ -93,13 +94,15 @@ def psd(data, fs, axis=-1, resolution=0.5, window="hann", overlap=0.5,
 _CROSS_PUSH_BYTES = 1 << 30
 
 
-def _cross_stream(data, fs, axis, resolution, window, overlap, detrend, scaling, begin, arrays=1):
+def _cross_stream(data, fs, axis, resolution, window, overlap, detrend, scaling, begin, arrays=1,
+                  at_least=1):
     """The Welch loop over all channel pairs that ``csd``, ``coherence`` and
     ``phase_connectivity`` share.  Checks the arguments (touching neither the stream nor the
     device), then calls ``begin(nch, nfreq)`` once -- it allocates the sums and returns the
     function every push's (nseg, nch, nfreq) complex128 spectra are handed to, which may
     overwrite them.  ``arrays``: how many complex128 (C, C, nfreq) arrays' worth of host memory
-    the result takes.  -> (cnt, freqs, nfft, host)."""
+    the result takes; ``at_least``: the segments the data's shape must promise.
+    -> (cnt, freqs, nfft, host)."""
     pro, nfft, freqs, stride, coeffs, scale, axis_n, layout = _welch_plan(
         data, fs, axis, resolution, window, overlap, scaling)
     if len(pro.shape) == 1:
@@ -113,6 +116,9 @@ def _cross_stream(data, fs, axis, resolution, window, overlap, detrend, scaling,
     if pro.shape[axis_n] < nfft:
         raise ValueError(f"no complete segment: {pro.shape[axis_n]} samples along axis {axis_n} are fewer "
                          f"than nfft = int(fs / resolution) = {nfft}")
+    if (pro.shape[axis_n] - nfft) // stride + 1 < at_least:
+        raise ValueError(f"the jackknife needs at least two segments: {pro.shape[axis_n]} samples along axis "
+                         f"{axis_n} hold one of nfft = {nfft} at a stride of {stride}")
     nch, nfreq = layout.nch, nfft // 2 + 1
     if dev.origin_is_host(pro):
         _host_result_fits(nch, nfreq, arrays)    # (before any work is done for it)
@@ -289,6 +295,141 @@ def phase_connectivity(data, fs, method="wpli", axis=-1, resolution=0.5, window=
             M = dev.phase_finish(m, cnt, nfft, **sums)
             out[m] = M.cpu().numpy() if host else M
     return cnt, freqs, out[names[0]] if isinstance(method, str) else out
+
+
+JACKKNIFE_METHODS = ("coherence",) + PHASE_METHODS
+
+
+def _jackknife_methods(method):
+    names = (method,) if isinstance(method, str) or not isinstance(method, (tuple, list)) else tuple(method)
+    bad = [m for m in names if not isinstance(m, str) or m not in JACKKNIFE_METHODS]
+    if bad or not names:
+        raise ValueError(f"unknown jackknife method(s) {bad}: choose from {JACKKNIFE_METHODS}")
+    return names
+
+
+def jackknife(data, fs, method="coherence", axis=-1, resolution=0.5, window="hann", overlap=0.5,
+              detrend="constant"):
+    """Coherence and phase connectivity over all channel pairs with their delete-one jackknife
+    standard errors over the Welch segments (Thomson & Chave 1991; Bokil et al. 2007).
+
+    ``data``, the segment cutting and the argument errors are those of ``csd``; ``method`` is one
+    of ``JACKKNIFE_METHODS`` = ``("coherence",) + PHASE_METHODS`` or a tuple of them.  Returns
+    ``(cnt, freqs, estimate, stderr)``: ``estimate`` is bit for bit what ``coherence`` /
+    ``phase_connectivity`` return for the same arguments, ``stderr`` is float64 (C, C, nfreq); a
+    tuple of names gives two dicts of name -> array.  Host data gives ndarrays, CUDA data CUDA
+    tensors.  Fewer than two segments raise ``ValueError`` (at least two segments are needed),
+    before the stream is started when the data's shape tells.
+
+    Definition.  With N = cnt segments, theta the measure from all of them, theta_(s) the
+    measure with segment s left out and d_s = theta_(s) - theta,
+
+        stderr^2 = (N - 1) / N (sum_s d_s^2 - (sum_s d_s)^2 / N),   clamped at 0,
+
+    the deviations taken from theta (the theta_(s) differ by O(1 / N): their own squares would
+    cancel).  The subtraction itself carries up to (3 N + 1) roundings of sum d_s^2: a difference
+    that does not exceed 4 N 2^-53 sum d_s^2 is written as 0 -- the theta_(s) are then equal to
+    within rounding, as with two segments, where coherence, plv, pli and wpli of the one segment
+    left are 1 whichever is left out.  Every measure is a function of sums over the segments, so theta_(s) is that
+    function of the totals minus segment s's contribution: with z_s = conj(X_i) X_j, d = Im z_s,
+    p_i = |X_i|^2, u_s = z_s / |z_s| and the totals A = sum z, P = sum p, U = sum u, D = sum d,
+    B = sum |d|, Q = sum d^2, G = sum sign d,
+
+    ``"coherence"``  |A - z_s|^2 / ((P_i - p_i)(P_j - p_j))
+    ``"imcoh"``      Im(A - z_s) / sqrt((P_i - p_i)(P_j - p_j))
+    ``"plv"``        |U - u_s| / (N - 1)
+    ``"pli"``        |G - sign d| / (N - 1)
+    ``"wpli"``       |D - d| / (B - |d|)
+    ``"dwpli"``      ((D - d)^2 - (Q - d^2)) / ((B - |d|)^2 - (Q - d^2))
+
+    A zero denominator gives NaN or inf, as IEEE does; with N = 2 dwpli's theta_(s) is 0 / 0
+    everywhere (written as NaN, not left to the rounding of the downdate) and so is its stderr.
+    Overlapping segments are not independent: with
+    ``overlap`` > 0 the jackknife treats correlated segments as independent draws and
+    understates the error; ``overlap=0`` gives the textbook jackknife.  No bias correction and no
+    variance-stabilising transform is applied; ``metrics.jackknife_interval`` turns ``stderr``
+    into a Student-t interval.
+
+    Two passes over ``data``, which must give the same stream twice (``RuntimeError`` if the
+    passes count different numbers of segments).  Pass 1 is ``coherence`` /
+    ``phase_connectivity``: the totals and the estimates.  Pass 2 cuts the same segments again
+    and per push adds d_s and d_s^2 of every (pair, bin) in segment order from the stored sums:
+    ``stderr`` has the same bits however the stream is chunked and two calls give the same bits.
+    It costs about what pass 1 costs with one kernel launch per method and push, plus the second
+    read of the stream.
+
+    Fixed points, written and not computed: the diagonal of ``stderr`` is 0.0; for every method
+    but plv it is 0.0 at f = 0, and at the Nyquist bin when nfft is even (the phase measures are
+    the constant 0 there; coherence at a real bin is a correlation of real numbers, with half the
+    degrees of freedom of the other bins, and gets no error bar).  NaN overrides them, as in
+    ``phase_connectivity``: with ``detrend="constant"`` a non-finite sample in channel k makes row
+    and column k of ``estimate`` and ``stderr`` NaN and leaves every other pair's bits as they
+    are; ``detrend="linear"`` raises ``ValueError`` then.  ``stderr`` is symmetric bit for bit
+    for every method (imcoh's deviations change sign together).
+
+    Device memory: the totals of ``phase_connectivity`` (16 B per (pair, bin) for coherence and
+    imcoh together, 16 B for plv, 32 B for pli, wpli and dwpli together), plus 16 B per (pair,
+    bin) per method for the two running sums, 8 B per returned array and per push the segment
+    spectra ``csd`` documents.
+    """
+    names = _jackknife_methods(method)
+    need_acc = any(m in names for m in ("coherence", "imcoh"))
+    need_plv = "plv" in names
+    need_lag = any(m in names for m in ("pli", "wpli", "dwpli"))
+    order = sorted(set(names), key=lambda m: (m == "plv", JACKKNIFE_METHODS.index(m)))   # plv last
+    sums, dev2 = {}, {}
+
+    def totals(nch, nfreq):
+        if need_acc:
+            sums["acc"] = dev.zeros((nch, nch, nfreq), dev.torch.complex128)
+        if need_plv:
+            sums["accn"] = dev.zeros((nch, nch, nfreq), dev.torch.complex128)
+        if need_lag:
+            sums["lag"] = dev.zeros((4, nch, nch, nfreq), dev.torch.float64)
+
+        def each(X):
+            if need_lag:
+                dev.lag_accumulate(X, sums["lag"])
+            if need_acc:
+                dev.cross_accumulate(X, sums["acc"])
+            if need_plv:
+                # last: the normalisation overwrites the push's spectra
+                dev.cross_accumulate(dev.unit_phasors(X), sums["accn"])
+        return each
+
+    # (an estimate and its stderr, float64 both, take one complex128 array's worth of host memory)
+    args = (data, fs, axis, resolution, window, overlap, detrend, "density")
+    cnt, freqs, nfft, host = _cross_stream(*args, totals, arrays=len(order), at_least=2)
+    if cnt < 2:
+        raise ValueError(f"the jackknife needs at least two segments: the stream held {cnt}")
+    estimate = {}
+    for m in order:
+        M = (dev.cross_finish(sums["acc"], cnt, nfft, _lib.CROSS_COHERENCE) if m == "coherence"
+             else dev.phase_finish(m, cnt, nfft, **sums))
+        estimate[m] = M.cpu().numpy() if host else M
+
+    def deviations(nch, nfreq):
+        for m in order:
+            dev2[m] = dev.zeros((2, nch, nch, nfreq), dev.torch.float64)
+
+        def each(X):
+            for m in order:
+                if m == "plv":
+                    dev.unit_phasors(X)          # last: the normalisation overwrites the push's spectra
+                dev.jackknife_accumulate(m, X, cnt, dev2[m], **sums)
+        return each
+
+    again, _, _, _ = _cross_stream(*args, deviations, arrays=len(order), at_least=2)
+    if again != cnt:
+        raise RuntimeError(f"the two passes of the jackknife counted {cnt} and {again} segments: the data "
+                           "must give the same stream every time it is iterated")
+    stderr = {}
+    for m in order:
+        E = dev.jackknife_finish(m, dev2.pop(m), cnt, nfft, **sums)
+        stderr[m] = E.cpu().numpy() if host else E
+    if isinstance(method, str):
+        return cnt, freqs, estimate[method], stderr[method]
+    return cnt, freqs, {m: estimate[m] for m in names}, {m: stderr[m] for m in names}
 
 
 def stft(data, fs, axis=-1, resolution=0.5, window="hann", overlap=0.5,

@@ -5,11 +5,13 @@ consumers of the PSD path.  Same signatures and results as the reference's
 device Simpson kernel (``osz_simpson``) and ``power_norm`` divides by it with
 ``osz_ew``; a CUDA estimate -- what ``psd`` returns for device input -- never
 leaves HBM, an ndarray estimate is uploaded and the result brought back.
-``confidence_interval`` scales by two chi-squared quantiles (host scalars).
+``confidence_interval`` scales by two chi-squared quantiles (host scalars);
+``jackknife_interval`` turns the standard errors of ``estimators.jackknife`` into a Student-t
+interval (one host scalar, the arithmetic stays where the arrays are).
 """
 
 import numpy as np
-from scipy.stats import chi2
+from scipy.stats import chi2, t
 
 from openseize_amd import _device as dev
 from openseize_amd import _lib
@@ -64,3 +66,14 @@ def confidence_interval(psd, n_estimates, alpha=0.05):
     lo_q, hi_q = chi2.ppf([alpha / 2, 1 - alpha / 2], dof)
     psd = np.asarray(psd.cpu() if dev.is_tensor(psd) else psd)
     return list(zip(psd * dof / lo_q, psd * dof / hi_q))
+
+
+def jackknife_interval(estimate, stderr, n_estimates, alpha=0.05):
+    """(lower, upper) = estimate -/+ t.ppf(1 - alpha / 2, n_estimates - 1) * stderr: the 1-alpha
+    interval of a jackknife over ``n_estimates`` segments (``estimators.jackknife``: its
+    ``estimate``, ``stderr`` and ``cnt``).  ndarrays give ndarrays, tensors tensors on their
+    device.  Nothing is clipped: the interval of a coherence near 0 may reach below 0."""
+    if n_estimates < 2:
+        raise ValueError("a jackknife interval needs at least two estimates")
+    half = float(t.ppf(1 - alpha / 2, n_estimates - 1)) * stderr
+    return estimate - half, estimate + half
