@@ -341,6 +341,13 @@ int osz_poly_set_state(osz_poly_t h, const double *state, void *stream);
 /* Number of output samples a push of n more input samples will produce
  * (final != 0: the stream ends with this push, total = ceil(N*L/M)). */
 int64_t osz_poly_out_count(osz_poly_t h, int64_t n, int final);
+/* The plan of this handle (read-only), for tests that check every compiled instance.  Fills
+ * out[0 .. n), n >= 9, with: kernel (0 the cache-path poly_kernel, 1 poly_block_kernel), ONE
+ * (L == 1), NT (output threads per tile), EG (phase groups), apad (taps per phase stream of the
+ * blocked table), se (LDS doubles per phase stream), lds_bytes -- the block kernel's, 0 for the
+ * fallback -- then H (samples of history carried) and half (the centre tap); the rest 0.
+ * 0 or an osz_status_t. */
+int osz_poly_plan(osz_poly_t h, int32_t *out, int n);
 int osz_poly_push(osz_poly_t h, const double *x, int64_t ldx, int64_t n,
                   int final, double *y, int64_t ldy, int64_t *n_out,
                   void *stream);

@@ -884,6 +884,18 @@ class PolyStream(_Handle):
             max(y.stride(0), 1), ctypes.byref(nout), stream_ptr()))
         return y
 
+    def reset(self):
+        """Back to the start of a stream: nothing consumed, zero history (C ABI: osz_poly_reset)."""
+        _lib.check(self.lib.osz_poly_reset(self.h, stream_ptr()))
+
+
+def poly_plan(stream):
+    """The plan of a PolyStream (C ABI: osz_poly_plan): kernel (0 the cache-path fallback, 1 the
+    block kernel), its instance ONE, NT, EG, apad, se, lds_bytes (0 for the fallback), H, half."""
+    out = (ctypes.c_int32 * 9)()
+    _lib.check(stream.lib.osz_poly_plan(stream.h, out, 9))
+    return dict(zip(("kernel", "ONE", "NT", "EG", "apad", "se", "lds_bytes", "H", "half"), out))
+
 
 class SpecStream(_Handle):
     """One iterator's segmenter / windowed-DFT state (C ABI: osz_spec_*)."""

@@ -116,6 +116,7 @@ SIGNATURES = {
     "osz_poly_get_state": (ctypes.c_int, [c_vp, c_dp, c_vp]),
     "osz_poly_set_state": (ctypes.c_int, [c_vp, c_dp, c_vp]),
     "osz_poly_out_count": (c_i64, [c_vp, c_i64, ctypes.c_int]),
+    "osz_poly_plan": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int]),
     "osz_poly_push": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, ctypes.c_int,
                                      c_vp, c_i64, ctypes.POINTER(c_i64), c_vp]),
     "osz_spec_create": (ctypes.c_int, [ctypes.POINTER(c_vp), ctypes.c_int,

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.h"
+#include "poly_plan.h"
 
 namespace osz {
 
@@ -72,8 +73,8 @@ __global__ __launch_bounds__(256) void poly_kernel(PolyArgs a) {
 // free, and every read of the blocked loop sits at a compile-time offset from
 // one per-block base address.  Results leave through LDS so that consecutive
 // lanes store consecutive outputs.
-constexpr int kPolyR = 4;                 // consecutive outputs per thread
-constexpr int kPolyBlk = 8;               // taps per coefficient block
+constexpr int kPolyR = polyplan::kR;      // consecutive outputs per thread
+constexpr int kPolyBlk = polyplan::kBlk;  // taps per coefficient block
 constexpr int kPolyBatch = 24;            // staging loads in flight per thread
 
 __device__ __forceinline__ int poly_pad(int i) { return i + (i >> 2); }
@@ -274,7 +275,7 @@ struct osz_poly_s {
     int m, L, M, nch, H, half;
     double *dhL;
     double *dG;         // blocked sub-filters for poly_block_kernel, or null
-    int apad, se, nt;   // nt: threads per workgroup (256, 128 or 64), 0 = kernel not usable
+    polyplan::Plan plan;   // nt: output threads per tile (256, 128 or 64), 0 = kernel not usable
     double *dhist[2];
     int cur;
     int64_t nin, nout;
@@ -308,7 +309,7 @@ int osz_poly_create_centred(osz_poly_t *h, const double *taps, int ntaps, int ce
     p->M = M;
     p->nch = nch;
     p->half = centre;
-    p->H = (ntaps - 1 + L - 1) / L + 1;
+    p->H = (ntaps - 1 + L - 1) / L + 1;      // (= polyplan::Plan::H)
     p->cur = 0;
     p->nin = p->nout = 0;
     std::vector<double> hL(ntaps);
@@ -320,78 +321,13 @@ int osz_poly_create_centred(osz_poly_t *h, const double *taps, int ntaps, int ce
     OSZ_HIP(hipMemcpy(p->dhL, hL.data(), sizeof(double) * ntaps, hipMemcpyHostToDevice));
     OSZ_HIP(hipMemset(p->dhist[0], 0, hb));
     OSZ_HIP(hipMemset(p->dhist[1], 0, hb));
-    // blocked sub-filters G[r][e][a] = hsub_r[msub_r - 1 - (M a + e)]
+    // tile, phase groups, stream pitch and the blocked sub-filters: poly_plan.h
     p->dG = nullptr;
-    {
-        const int msub_max = (ntaps + L - 1) / L;
-        int apad = (msub_max + M - 1) / M;                       // taps per phase stream
-        apad = (apad + kPolyBlk - 1) / kPolyBlk * kPolyBlk;
-        p->apad = apad;
-        p->nt = 0;
-        p->se = 0;
-        for (int nt = 256; nt >= 64 && !p->nt; nt >>= 1) {
-            const int nstream = nt * kPolyR + apad;
-            const int se = (nstream + (nstream >> 2) + 2) | 1;   // odd: spreads the staging writes
-            const size_t bytes = ((size_t)M * se + (L == 1 ? 0 : (size_t)nt * kPolyR * L)) * sizeof(double);
-            // (the smallest tile may take most of a CU's 160 KB: one workgroup per CU then, still
-            // fifty times the rate of the kernel that reads its window through the caches)
-            if (bytes <= (nt == 64 ? 150 : 53) * 1024) {
-                p->nt = nt;
-                p->se = se;
-            }
-        }
-        if (p->nt) {
-            // The stream pitch decides how the staging writes fall on the banks: a ds_write_b64
-            // is served in groups of 16 consecutive lanes, conflict free when their 16 double
-            // addresses e * se + pad(i) differ mod 16 (MI355X_MICROARCH.md, LDS).  Lanes walk
-            // (i, e) = (w div M, w mod M), so the best pitch depends on M: take, among the 16
-            // pitches from the needed one up, the one with the fewest extra LDS cycles over the
-            // first steps of a tile (it was "any odd pitch": 30 % of the LDS cycles were conflicts).
-            // (threads per workgroup as osz_poly_push launches it: its phase-group rule)
-            const size_t blds0 = ((size_t)M * p->se + (L == 1 ? 0 : (size_t)p->nt * kPolyR * L)) * sizeof(double);
-            const int eg_on0 = blds0 > 53 * 1024 ? 4 : 2;
-            const int nth = p->nt * ((L == 1 && p->nt <= 128) ? (eg_on0 >= 4 && M >= 4 ? 4 : M >= 2 ? 2 : 1) : 1);
-            const int stepw = nth - nth % M, dqs = M <= nth ? stepw / M : 0;
-            auto extra_cycles = [&](int se) {
-                long cost = 0;
-                for (int u = 0; u < 8; ++u)
-                    for (int g0 = 0; g0 < nth; g0 += 16) {
-                        int cnt[16] = {0}, worst = 0;
-                        for (int tw = g0; tw < g0 + 16 && tw < nth; ++tw) {
-                            const int i = tw / M + u * dqs, e = tw % M;
-                            const int bank = (int)(((long)e * se + i + (i >> 2)) & 15);
-                            worst = std::max(worst, ++cnt[bank]);
-                        }
-                        cost += worst - 1;
-                    }
-                return cost;
-            };
-            if (M <= nth) {
-                int best = p->se;
-                long best_cost = extra_cycles(best);
-                for (int cand = p->se + 1; cand < p->se + 16 && best_cost > 0; ++cand) {
-                    const size_t bytes = ((size_t)M * cand + (L == 1 ? 0 : (size_t)p->nt * kPolyR * L)) * sizeof(double);
-                    if (bytes > (size_t)(p->nt == 64 ? 150 : 53) * 1024) break;
-                    const long c = extra_cycles(cand);
-                    if (c < best_cost) {
-                        best_cost = c;
-                        best = cand;
-                    }
-                }
-                p->se = best;
-            }
-            std::vector<double> G((size_t)L * M * apad, 0.0);
-            for (int r = 0; r < L; ++r) {
-                const int phi = (int)(((int64_t)r * M + p->half) % L);
-                const int msub = phi < ntaps ? (ntaps - phi + L - 1) / L : 0;
-                for (int kk = 0; kk < msub; ++kk) {
-                    const int u = msub - 1 - kk, aa = u / M, e = u % M;
-                    G[((size_t)r * M + e) * apad + aa] = hL[phi + (size_t)L * kk];
-                }
-            }
-            OSZ_HIP(hipMalloc(&p->dG, G.size() * sizeof(double)));
-            OSZ_HIP(hipMemcpy(p->dG, G.data(), G.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
+    p->plan = polyplan::plan(ntaps, L, M);
+    if (p->plan.nt) {
+        const std::vector<double> G = polyplan::build_G(hL.data(), ntaps, p->half, L, M, p->plan.apad);
+        OSZ_HIP(hipMalloc(&p->dG, G.size() * sizeof(double)));
+        OSZ_HIP(hipMemcpy(p->dG, G.data(), G.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     *h = p;
     return OSZ_OK;
@@ -443,6 +379,24 @@ int osz_poly_set_state(osz_poly_t h, const double *state, void *stream) {
     return OSZ_OK;
 }
 
+int osz_poly_plan(osz_poly_t h, int32_t *out, int n) {
+    OSZ_REQUIRE(h && out && n >= 9, "osz_poly_plan: null argument or n=%d < 9", n);
+    for (int i = 0; i < n; ++i) out[i] = 0;
+    const polyplan::Plan &pl = h->plan;
+    out[0] = h->dG ? 1 : 0;
+    if (h->dG) {
+        out[1] = h->L == 1;
+        out[2] = pl.nt;
+        out[3] = pl.eg;
+        out[4] = pl.apad;
+        out[5] = pl.se;
+        out[6] = (int32_t)pl.lds;
+    }
+    out[7] = h->H;
+    out[8] = h->half;
+    return OSZ_OK;
+}
+
 int64_t osz_poly_out_count(osz_poly_t h, int64_t n, int final_) {
     if (!h || n < 0) return -1;
     return poly_end(h, h->nin + n, final_) - h->nout;
@@ -477,32 +431,26 @@ int osz_poly_push(osz_poly_t h, const double *x, int64_t ldx, int64_t n, int fin
         a.H = h->H;
         a.half = h->half;
         if (h->dG) {
-            PolyBlockArgs b{a, h->dG, h->apad, h->se, 0, 0};
-            const size_t blds = sizeof(double) * ((size_t)h->M * h->se +
-                                                  (h->L == 1 ? 0 : (size_t)h->nt * kPolyR * h->L));
+            const polyplan::Plan &pl = h->plan;
+            PolyBlockArgs b{a, h->dG, pl.apad, pl.se, pl.stepw, pl.dqs};
+            const size_t blds = pl.lds;
             using kern_t = void (*)(PolyBlockArgs);
             static const kern_t kerns[2][3] = {
                 {poly_block_kernel<false, 256>, poly_block_kernel<false, 128>, poly_block_kernel<false, 64>},
                 {poly_block_kernel<true, 256>, poly_block_kernel<true, 128>, poly_block_kernel<true, 64>}};
-            // decimators on a 128- or 64-thread tile: two (or four) phase groups
+            // decimators on a 128- or 64-thread tile: two (or four) phase groups (polyplan::phase_groups)
             static const kern_t kerns2[2][2] = {
                 {poly_block_kernel<true, 128, 2>, poly_block_kernel<true, 64, 2>},
                 {poly_block_kernel<true, 128, 4>, poly_block_kernel<true, 64, 4>}};
-            // two phase groups per workgroup (four measured no faster); four when the window
-            // leaves room for one or two workgroups per CU only
-            const int eg_on = blds > 53 * 1024 ? 4 : 2;
-            const int eg = (h->L == 1 && h->nt <= 128) ? (eg_on >= 4 && h->M >= 4 ? 4 : eg_on >= 2 && h->M >= 2 ? 2 : 1) : 1;
-            const bool split = eg > 1;
-            const kern_t kern = split ? kerns2[eg == 4 ? 1 : 0][h->nt == 128 ? 0 : 1]
-                                      : kerns[h->L == 1 ? 1 : 0][h->nt == 256 ? 0 : h->nt == 128 ? 1 : 2];
-            b.stepw = eg * h->nt - (eg * h->nt) % h->M;
-            b.dqs = b.stepw / h->M;
+            const int eg = pl.eg, nt = pl.nt;
+            const kern_t kern = eg > 1 ? kerns2[eg == 4 ? 1 : 0][nt == 128 ? 0 : 1]
+                                       : kerns[h->L == 1 ? 1 : 0][nt == 256 ? 0 : nt == 128 ? 1 : 2];
             OSZ_DYN_LDS(kern, blds > 64 * 1024 ? blds : 64 * 1024);
-            const int64_t per = (int64_t)h->nt * kPolyR * h->L;
+            const int64_t per = (int64_t)nt * kPolyR * h->L;
             const int64_t bx = (cnt + per - 1) / per;
             KernelTimer kt("poly_block", st);
             hipLaunchKernelGGL(kern,
-                               dim3((unsigned)bx, h->nch), dim3(eg * h->nt), blds, st, b);
+                               dim3((unsigned)bx, h->nch), dim3(eg * nt), blds, st, b);
         } else {   // very large M: the window of even a 64-thread tile exceeds LDS
             int64_t bx = (cnt + 255) / 256;
             if (bx > 4096) bx = 4096;
