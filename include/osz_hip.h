@@ -653,6 +653,50 @@ int osz_jackknife_accumulate(int mode, const void *X, int64_t nseg, int nch, int
 int osz_jackknife_finish(int mode, const double *dev2, const void *acc, const void *accn, const double *lag,
                          int64_t count, int nch, int nfreq, int nfft_is_even, double *out, void *stream);
 
+/* ---- time-domain connectivity of analytic signals over all channel pairs ------------------ */
+/* (experimental/coupling/connectivity.py analytic_connectivity; csrc/pairtime.hip, K13) */
+#define OSZ_ANALYTIC_BLOCK 4096   /* samples per time block, counted from the stream's first sample */
+typedef enum {                    /* sum groups, a bit each; their planes follow in this order      */
+    OSZ_ANALYTIC_AMP = 1,         /* 1 plane:  sum a_i a_j                                           */
+    OSZ_ANALYTIC_ORTH = 2,        /* 5 planes: sum m, m / a_i, m / a_j, (m / a_i)^2, (m / a_j)^2     */
+    OSZ_ANALYTIC_LOCK = 4,        /* 2 planes: Re, Im of sum conj(u_i) u_j                           */
+    OSZ_ANALYTIC_LAG = 8,         /* 2 planes: sum d, sum m                                          */
+    OSZ_ANALYTIC_ALL = 15
+} osz_analytic_group;
+typedef enum {
+    OSZ_ANALYTIC_AEC = 0,         /* Pearson r of (a_i, a_j)                             reads AMP  */
+    OSZ_ANALYTIC_OAEC = 1,        /* (r(a_i, m / a_i) + r(a_j, m / a_j)) / 2             reads ORTH */
+    OSZ_ANALYTIC_PLV = 2,         /* |sum conj(u_i) u_j| / count                         reads LOCK */
+    OSZ_ANALYTIC_CIPLV = 3,       /* |Im s| / sqrt(1 - (Re s)^2), s = sum / count        reads LOCK */
+    OSZ_ANALYTIC_WPLI = 4         /* |sum d| / sum m                                     reads LAG  */
+} osz_analytic_mode;
+/*
+ * The doubles of work space one push of n samples of nch channels with these groups needs
+ * (the staged planes, the block partials); -1 for arguments out of range.
+ */
+int64_t osz_analytic_work(int nch, int64_t n, int groups);
+/*
+ * z: nch rows of n c128 samples (device, interleaved re/im), row pitch ld samples.  With
+ * a = |z|, u = z / a, d = Im(conj(z_i) z_j) = fma(x_i, y_j, -(y_i x_j)) and m = |d|, adds for i <= j
+ * the sums over the n samples that `groups` names to sums -- (planes, nch, nch) f64 (device), the
+ * planes of the groups present in the order above, owned and zeroed by the caller -- and sum a,
+ * sum a^2 and sum |u|^2 of every channel to chan (3, nch).  Entries of sums with i > j are not
+ * touched.  The samples are summed in blocks of OSZ_ANALYTIC_BLOCK in a fixed order and the
+ * blocks' partials added to the stored sums in block order, no atomics: when every push but a
+ * stream's last holds a whole number of blocks, the sums do not depend on where the stream is
+ * cut and two runs give the same bits.  work: at least work_len >= the doubles the work-space
+ * query above asks for (device), contents undefined afterwards.
+ */
+int osz_analytic_accumulate(const void *z, int64_t ld, int nch, int64_t n, int groups, double *sums,
+                            double *chan, double *work, int64_t work_len, void *stream);
+/*
+ * out (nch, nch) f64 from the sums of `count` samples; out[j, i] = out[i, j].  In this order:
+ * where one of the sums in chan of channel i or j is not finite the entry is NaN; the diagonal is
+ * 1.0 for aec and plv and 0.0 for the others; elsewhere the definition, 0 / 0 left as NaN.
+ */
+int osz_analytic_finish(int mode, const double *sums, int groups, const double *chan, int64_t count,
+                        int nch, double *out, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

@@ -1350,3 +1350,44 @@ def jackknife_finish(method, dev2, count, nfft, acc=None, accn=None, lag=None):
                                         *(ptr(t) if t is not None else None for t in (acc, accn, lag)),
                                         int(count), nch, nfreq, int(nfft % 2 == 0), ptr(out), stream_ptr()))
     return out
+
+
+def analytic_planes(groups):
+    """The (nch, nch) planes of sums the sum groups in the bit mask ``groups`` keep together."""
+    return sum(n for g, n in _lib.ANALYTIC_PLANES.items() if groups & g)
+
+
+def analytic_accumulate(z2d, groups, sums, chan):
+    """osz_analytic_accumulate: adds the sums over the samples of z2d -- (nch, n) complex128 CUDA
+    rows, unit stride along n -- that the sum groups ``groups`` name to ``sums`` (planes, nch,
+    nch) for i <= j, and the per-channel sums to ``chan`` (3, nch); both float64, contiguous.
+    Every push of a stream but its last must hold a whole number of _lib.ANALYTIC_BLOCK samples
+    for the sums not to depend on the cuts."""
+    lib = require_gpu()
+    nch, n = z2d.shape
+    planes = analytic_planes(groups)
+    if z2d.dtype != torch.complex128 or (n > 1 and z2d.stride(1) != 1) or (nch > 1 and z2d.stride(0) < n):
+        raise ValueError(f"analytic_accumulate: z {tuple(z2d.shape)} {z2d.dtype} is not complex128 (nch, n) rows")
+    if (sums.dtype != torch.float64 or chan.dtype != torch.float64 or tuple(sums.shape) != (planes, nch, nch)
+            or tuple(chan.shape) != (3, nch) or not sums.is_contiguous() or not chan.is_contiguous()):
+        raise ValueError(f"analytic_accumulate: sums {tuple(sums.shape)} / chan {tuple(chan.shape)} are not "
+                         f"contiguous float64 ({planes}, {nch}, {nch}) / (3, {nch})")
+    need = lib.osz_analytic_work(nch, n, groups)
+    if need < 0:
+        raise ValueError(f"analytic_accumulate: bad sizes or sum groups ({nch}, {n}, {groups})")
+    work = torch.empty(max(need, 1), dtype=torch.float64, device=z2d.device)
+    _lib.check(lib.osz_analytic_accumulate(ptr(z2d), max(z2d.stride(0), n) if nch > 1 else n, nch, n, groups,
+                                           ptr(sums), ptr(chan), ptr(work), need, stream_ptr()))
+
+
+def analytic_finish(method, count, groups, sums, chan):
+    """osz_analytic_finish: the float64 (nch, nch) measure ``method`` (a key of
+    _lib.ANALYTIC_MODE) from the sums of ``count`` samples that analytic_accumulate kept."""
+    lib = require_gpu()
+    nch = chan.shape[1]
+    if tuple(sums.shape) != (analytic_planes(groups), nch, nch) or not sums.is_contiguous() or not chan.is_contiguous():
+        raise ValueError(f"analytic_finish: sums {tuple(sums.shape)} do not hold the planes of groups {groups}")
+    out = torch.empty((nch, nch), dtype=torch.float64, device=sums.device)
+    _lib.check(lib.osz_analytic_finish(_lib.ANALYTIC_MODE[method], ptr(sums), groups, ptr(chan), int(count), nch,
+                                       ptr(out), stream_ptr()))
+    return out

@@ -27,6 +27,13 @@ DETREND = {"constant": 0, "linear": 1}
 CROSS_SPECTRUM, CROSS_COHERENCE = 0, 1
 PHASE_MODE = {"imcoh": 0, "plv": 1, "pli": 2, "wpli": 3, "dwpli": 4}
 JACK_MODE = {"coherence": 0, "imcoh": 1, "plv": 2, "pli": 3, "wpli": 4, "dwpli": 5}
+ANALYTIC_MODE = {"aec": 0, "oaec": 1, "plv": 2, "ciplv": 3, "wpli": 4}
+# the sum group (a bit) each analytic measure reads, and the (nch, nch) planes a group keeps
+ANALYTIC_AMP, ANALYTIC_ORTH, ANALYTIC_LOCK, ANALYTIC_LAG = 1, 2, 4, 8
+ANALYTIC_GROUP = {"aec": ANALYTIC_AMP, "oaec": ANALYTIC_ORTH, "plv": ANALYTIC_LOCK, "ciplv": ANALYTIC_LOCK,
+                  "wpli": ANALYTIC_LAG}
+ANALYTIC_PLANES = {ANALYTIC_AMP: 1, ANALYTIC_ORTH: 5, ANALYTIC_LOCK: 2, ANALYTIC_LAG: 2}
+ANALYTIC_BLOCK = 4096
 
 
 class OszLibraryError(RuntimeError):
@@ -177,6 +184,11 @@ SIGNATURES = {
                                                 c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "osz_jackknife_finish": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "osz_analytic_work": (c_i64, [ctypes.c_int, c_i64, ctypes.c_int]),
+    "osz_analytic_accumulate": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, ctypes.c_int, c_vp, c_vp, c_vp,
+                                               c_i64, c_vp]),
+    "osz_analytic_finish": (ctypes.c_int, [ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_i64, ctypes.c_int, c_vp,
+                                           c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),
