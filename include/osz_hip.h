@@ -697,6 +697,43 @@ int osz_analytic_accumulate(const void *z, int64_t ld, int nch, int64_t n, int g
 int osz_analytic_finish(int mode, const double *sums, int groups, const double *chan, int64_t count,
                         int nch, double *out, void *stream);
 
+/* ---- Welch bispectrum and bicoherence per channel (spectra/estimators.py bispectrum) ----- */
+/* (csrc/bispec.hip, K14) */
+typedef enum {
+    OSZ_BISPEC_SPECTRUM = 0,   /* out: (nch, nb, nb) c128   sum T / count                         */
+    OSZ_BISPEC_KIM = 1,        /* out: (nch, nb, nb) f64    |sum T|^2 / (sum |X1 X2|^2 sum |X3|^2) */
+    OSZ_BISPEC_HAGIHIRA = 2    /* out: (nch, nb, nb) f64    |sum T| / sum |T|                      */
+} osz_bispec_mode;
+/*
+ * The doubles of work space one push of nseg segments needs (the plane |X|); -1 for arguments
+ * out of range (nch * nfreq must stay below 2^27).
+ */
+int64_t osz_bispec_work(int64_t nseg, int nch, int nfreq);
+/*
+ * X: the (nseg, nch, nfreq) interleaved c128 block an OSZ_SPEC_DFT_SEGMENTS push wrote (device).
+ * The band is the nb bins k_lo .. k_lo + nb - 1 (k_lo + nb <= nfreq).  With k1 = k_lo + a,
+ * k2 = k_lo + b, X1 = X[s, c, k1], X2 = X[s, c, k2], X3 = X[s, c, k1 + k2] and T = X1 X2 conj(X3),
+ * for b <= a and k1 + k2 <= nfreq - 1 (the third factor is read from the whole spectrum):
+ *   sums[0, c, a, b] += sum over s of Re T         sums[1, c, a, b] += sum over s of Im T
+ *   sums[2, c, a, b] += sum over s of |X1 X2|^2    sums[3, c, a, b] += sum over s of |X1| |X2| |X3|
+ * and for every bin  power[c, k] += sum over s of |X[s, c, k]|^2.
+ * sums: (4, nch, nb, nb) f64, power: (nch, nfreq) f64 (device), owned and zeroed by the caller and
+ * carried across the pushes of a stream; entries of sums with b > a or outside the domain are
+ * not touched.  Summed segment by segment from the stored value, fused multiply-adds in a fixed
+ * order, no atomics: the sums do not depend on where the stream is cut and two runs give the
+ * same bits.  work: at least work_len >= the doubles the work-space query above asks for (device),
+ * contents undefined afterwards.
+ */
+int osz_bispec_accumulate(const void *X, int64_t nseg, int nch, int nfreq, int k_lo, int nb, double *sums,
+                          double *power, double *work, int64_t work_len, void *stream);
+/*
+ * out (nch, nb, nb), c128 for OSZ_BISPEC_SPECTRUM and f64 otherwise, from the sums of `count`
+ * segments as the table of modes says; out[c, b, a] = out[c, a, b] bit for bit.  Entries with
+ * k1 + k2 > nfreq - 1 are NaN (both parts of a c128).  A zero denominator gives what IEEE gives.
+ */
+int osz_bispec_finish(int mode, const double *sums, const double *power, int64_t count, int nch, int nfreq,
+                      int k_lo, int nb, void *out, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

@@ -1391,3 +1391,46 @@ def analytic_finish(method, count, groups, sums, chan):
     _lib.check(lib.osz_analytic_finish(_lib.ANALYTIC_MODE[method], ptr(sums), groups, ptr(chan), int(count), nch,
                                        ptr(out), stream_ptr()))
     return out
+
+
+def bispec_accumulate(X, k_lo, nb, sums, power):
+    """osz_bispec_accumulate: with T = X[s, c, k1] X[s, c, k2] conj(X[s, c, k1 + k2]), k1 = k_lo +
+    a and k2 = k_lo + b, adds for b <= a and k1 + k2 <= nfreq - 1 the sums over s of Re T, Im T,
+    |X1 X2|^2 and |X1| |X2| |X3| to sums[0 .. 3, c, a, b], and the sums of |X|^2 to power[c, k].
+    X: (nseg, nch, nfreq) complex128, sums: (4, nch, nb, nb) float64, power: (nch, nfreq)
+    float64, contiguous CUDA tensors."""
+    lib = require_gpu()
+    nseg, nch, nfreq = X.shape
+    if (X.dtype != torch.complex128 or sums.dtype != torch.float64 or power.dtype != torch.float64
+            or tuple(sums.shape) != (4, nch, nb, nb) or tuple(power.shape) != (nch, nfreq)
+            or not X.is_contiguous() or not sums.is_contiguous() or not power.is_contiguous()):
+        raise ValueError(f"bispec_accumulate: X {tuple(X.shape)} / sums {tuple(sums.shape)} / power "
+                         f"{tuple(power.shape)} are not contiguous complex128 (nseg, nch, nfreq) / float64 "
+                         f"(4, nch, {nb}, {nb}) / (nch, nfreq)")
+    need = lib.osz_bispec_work(nseg, nch, nfreq)
+    if need < 0:
+        raise ValueError(f"bispec_accumulate: bad sizes ({nseg}, {nch}, {nfreq})")
+    work = torch.empty(max(need, 1), dtype=torch.float64, device=X.device)
+    _lib.check(lib.osz_bispec_accumulate(ptr(X), nseg, nch, nfreq, int(k_lo), int(nb), ptr(sums), ptr(power),
+                                         ptr(work), need, stream_ptr()))
+
+
+def bispec_finish(mode, count, k_lo, sums, power):
+    """osz_bispec_finish: ``mode`` (a key of _lib.BISPEC_MODE) from the sums of ``count`` segments
+    that bispec_accumulate kept: "spectrum" the complex128 (nch, nb, nb) mean bispectrum, "kim" and
+    "hagihira" the float64 bicoherences; symmetric in the last two axes, NaN where k1 + k2 >
+    nfreq - 1."""
+    lib = require_gpu()
+    if mode not in _lib.BISPEC_MODE:
+        raise ValueError(f"bispec_finish: unknown mode {mode!r}: choose from {tuple(_lib.BISPEC_MODE)}")
+    nch, nfreq = power.shape
+    nb = sums.shape[-1]
+    if (tuple(sums.shape) != (4, nch, nb, nb) or sums.dtype != torch.float64 or power.dtype != torch.float64
+            or not sums.is_contiguous() or not power.is_contiguous()):
+        raise ValueError(f"bispec_finish: sums {tuple(sums.shape)} / power {tuple(power.shape)} are not contiguous "
+                         "float64 (4, nch, nb, nb) / (nch, nfreq)")
+    out = torch.empty((nch, nb, nb), dtype=torch.complex128 if mode == "spectrum" else torch.float64,
+                      device=sums.device)
+    _lib.check(lib.osz_bispec_finish(_lib.BISPEC_MODE[mode], ptr(sums), ptr(power), int(count), nch, nfreq,
+                                     int(k_lo), nb, ptr(out), stream_ptr()))
+    return out

@@ -34,6 +34,7 @@ ANALYTIC_GROUP = {"aec": ANALYTIC_AMP, "oaec": ANALYTIC_ORTH, "plv": ANALYTIC_LO
                   "wpli": ANALYTIC_LAG}
 ANALYTIC_PLANES = {ANALYTIC_AMP: 1, ANALYTIC_ORTH: 5, ANALYTIC_LOCK: 2, ANALYTIC_LAG: 2}
 ANALYTIC_BLOCK = 4096
+BISPEC_MODE = {"spectrum": 0, "kim": 1, "hagihira": 2}
 
 
 class OszLibraryError(RuntimeError):
@@ -189,6 +190,11 @@ SIGNATURES = {
                                                c_i64, c_vp]),
     "osz_analytic_finish": (ctypes.c_int, [ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_i64, ctypes.c_int, c_vp,
                                            c_vp]),
+    "osz_bispec_work": (c_i64, [c_i64, ctypes.c_int, ctypes.c_int]),
+    "osz_bispec_accumulate": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "osz_bispec_finish": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, c_vp, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

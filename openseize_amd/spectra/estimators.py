@@ -10,6 +10,8 @@ average taken over every PAIR of channels (K10), with ``scipy.signal.csd`` /
 ``scipy.signal.coherence`` as the yardstick.  ``phase_connectivity`` (K11) takes the
 phase-based measures (imcoh, plv, pli, wpli, dwpli) from the same segments, and ``jackknife``
 (K12) gives coherence and those five their delete-one standard errors in a second pass.
+``bispectrum`` and ``bicoherence`` (K14) are the third-order Welch average of every channel by
+itself, X(f1) X(f2) conj X(f1 + f2) over a band of bin pairs, from the same segments.
 """
 
 import numpy as np
@@ -95,20 +97,29 @@ _CROSS_PUSH_BYTES = 1 << 30
 
 
 def _cross_stream(data, fs, axis, resolution, window, overlap, detrend, scaling, begin, arrays=1,
-                  at_least=1):
+                  at_least=1, per_channel=None):
     """The Welch loop over all channel pairs that ``csd``, ``coherence`` and
     ``phase_connectivity`` share.  Checks the arguments (touching neither the stream nor the
     device), then calls ``begin(nch, nfreq)`` once -- it allocates the sums and returns the
     function every push's (nseg, nch, nfreq) complex128 spectra are handed to, which may
     overwrite them.  ``arrays``: how many complex128 (C, C, nfreq) arrays' worth of host memory
     the result takes; ``at_least``: the segments the data's shape must promise.
+    ``per_channel``: None for the estimators over channel PAIRS, or what a per-channel estimator
+    (``bispectrum``) changes -- one-dimensional data is one channel (noted in ``flat``), and the object's
+    ``host_fits(nch)`` / ``device_fits(nch)`` (the latter right after the device is found) and
+    ``push_bytes`` (device bytes a push takes per (segment, channel, bin)) replace the pairs'.
     -> (cnt, freqs, nfft, host)."""
     pro, nfft, freqs, stride, coeffs, scale, axis_n, layout = _welch_plan(
         data, fs, axis, resolution, window, overlap, scaling)
-    if len(pro.shape) == 1:
+    if per_channel is not None:
+        per_channel.flat = len(pro.shape) == 1
+        if len(pro.shape) > 2:
+            raise ValueError(f"the bispectrum needs one- or two-dimensional data (channels x samples), got shape "
+                             f"{tuple(pro.shape)}: reshape the channel axes into one")
+    elif len(pro.shape) == 1:
         raise ValueError("cross-spectra need two-dimensional data (channels x samples); "
                          "for a single channel use psd")
-    if len(pro.shape) != 2:
+    elif len(pro.shape) != 2:
         raise ValueError(f"cross-spectra need two-dimensional data (channels x samples), got shape "
                          f"{tuple(pro.shape)}: reshape the channel axes into one")
     if detrend not in _lib.DETREND:
@@ -120,12 +131,17 @@ def _cross_stream(data, fs, axis, resolution, window, overlap, detrend, scaling,
         raise ValueError(f"the jackknife needs at least two segments: {pro.shape[axis_n]} samples along axis "
                          f"{axis_n} hold one of nfft = {nfft} at a stride of {stride}")
     nch, nfreq = layout.nch, nfft // 2 + 1
+    host_fits = (lambda: _host_result_fits(nch, nfreq, arrays)) if per_channel is None else (
+        lambda: per_channel.host_fits(nch))
     if dev.origin_is_host(pro):
-        _host_result_fits(nch, nfreq, arrays)    # (before any work is done for it)
+        host_fits()                              # (before any work is done for it)
     dev.require_gpu()
+    if per_channel is not None:
+        per_channel.device_fits(nch)
     spec = dev.SpecStream(nfft, nfft, stride, coeffs, scale, detrend, _lib.SPEC_DFT_SEGMENTS, nch)
     feed = _Feed(pro, axis_n, layout)
-    cap = max(1, _CROSS_PUSH_BYTES // (16 * nch * nfreq)) * stride
+    push_bytes = 16 if per_channel is None else per_channel.push_bytes
+    cap = max(1, _CROSS_PUSH_BYTES // (push_bytes * nch * nfreq)) * stride
     cnt = 0
     try:
         each = begin(nch, nfreq)
@@ -145,7 +161,7 @@ def _cross_stream(data, fs, axis, resolution, window, overlap, detrend, scaling,
         raise ValueError(f"no complete segment: the stream ended before nfft = int(fs / resolution) = {nfft} "
                          "samples")
     if feed.host:
-        _host_result_fits(nch, nfreq, arrays)
+        host_fits()
     return cnt, freqs, nfft, feed.host
 
 
@@ -430,6 +446,148 @@ def jackknife(data, fs, method="coherence", axis=-1, resolution=0.5, window="han
     if isinstance(method, str):
         return cnt, freqs, estimate[method], stderr[method]
     return cnt, freqs, {m: estimate[m] for m in names}, {m: stderr[m] for m in names}
+
+
+BICOHERENCE_METHODS = tuple(m for m in _lib.BISPEC_MODE if m != "spectrum")        # ("kim", "hagihira")
+
+
+def _bicoherence_methods(method):
+    names = (method,) if isinstance(method, str) or not isinstance(method, (tuple, list)) else tuple(method)
+    bad = [m for m in names if not isinstance(m, str) or m not in BICOHERENCE_METHODS]
+    if bad or not names:
+        raise ValueError(f"unknown bicoherence method(s) {bad}: choose from {BICOHERENCE_METHODS}")
+    return names
+
+
+class _BispecPlan:
+    """The band of ``bispectrum`` / ``bicoherence`` and what ``_cross_stream`` asks a per-channel
+    estimator: the memory checks and the bytes of a push.  Touches neither stream nor device."""
+
+    push_bytes = 24        # 16 B of spectra and the 8 B of the plane |X| per (segment, channel, bin)
+
+    def __init__(self, fs, resolution, fmin, fmax, out_bytes):
+        nfft = int(fs / resolution)
+        freqs = np.fft.rfftfreq(nfft, 1 / fs)
+        if fmin is not None and fmax is not None and fmin > fmax:
+            raise ValueError(f"fmin = {fmin} is above fmax = {fmax}")
+        inside = np.ones(freqs.size, dtype=bool)
+        if fmin is None:
+            inside[:1] = False       # DC: under detrending what rounding left of a removed mean
+        else:
+            inside &= freqs >= fmin
+        if fmax is not None:
+            inside &= freqs <= fmax
+        bins = np.flatnonzero(inside)
+        if bins.size == 0:
+            raise ValueError(f"no bin of the {freqs.size} (spacing {fs / nfft:g} Hz) lies in the band "
+                             f"fmin = {fmin}, fmax = {fmax}")
+        self.k_lo, self.nb, self.out_bytes = int(bins[0]), int(bins.size), out_bytes
+        self.freqs = freqs[self.k_lo:self.k_lo + self.nb]
+
+    def _refuse(self, nch, what, need, have):
+        raise MemoryError(f"the bispectral {what} of {nch} channel(s) x {self.nb} x {self.nb} band-bin pairs need "
+                          f"{need / 1e9:.2f} GB, more than the {have} available: lower fmax (the pairs grow "
+                          "with the square of the band) or select fewer channels")
+
+    def host_fits(self, nch):
+        if not assignable((self.out_bytes // 8, nch, self.nb, self.nb), dtype=float, msg=False):
+            self._refuse(nch, "results", self.out_bytes * nch * self.nb ** 2, "host memory")
+
+    def device_fits(self, nch):
+        need = (32 + self.out_bytes) * nch * self.nb ** 2           # the four sums and the results
+        free = dev.torch.cuda.mem_get_info()[0]
+        if need > free:
+            self._refuse(nch, "sums (32 B per channel and pair) and results", need,
+                         f"{free / 1e9:.2f} GB of device memory")
+
+
+def _bispec_sums(plan, data, fs, axis, resolution, window, overlap, detrend, scaling):
+    """-> (cnt, sums (4, C, nb, nb) and power (C, nfreq) on the device, host): what ``bispectrum`` and ``bicoherence`` take from the Welch loop."""
+    kept = []
+
+    def begin(nch, nfreq):
+        sums = dev.zeros((4, nch, plan.nb, plan.nb), dev.torch.float64)
+        power = dev.zeros((nch, nfreq), dev.torch.float64)
+        kept.extend((sums, power))
+        return lambda X: dev.bispec_accumulate(X, plan.k_lo, plan.nb, sums, power)
+
+    cnt, _, _, host = _cross_stream(data, fs, axis, resolution, window, overlap, detrend, scaling, begin,
+                                    per_channel=plan)
+    return cnt, kept[0], kept[1], host
+
+
+def _bispec_result(M, host, flat):
+    M = M[0] if flat else M
+    return M.cpu().numpy() if host else M
+
+
+def bispectrum(data, fs, axis=-1, resolution=0.5, window="hann", overlap=0.5,
+               detrend="constant", scaling="density", fmin=None, fmax=None):
+    """Welch-averaged bispectrum of every channel: quadratic phase coupling between the rhythms
+    at f1, f2 and f1 + f2.
+
+    ``data`` is anything ``producer`` takes, one-dimensional (one channel) or two-dimensional
+    (samples along ``axis``, the C channels along the other axis).  Segments are cut as in ``psd``
+    and ``csd`` (nfft = int(fs / resolution), stride = nfft - int(nfft * overlap), a trailing
+    partial segment dropped) and X[s, c, k] is the segment spectrum ``csd`` sums: detrended,
+    windowed, ``rfft``, times the square root of the scaling's norm.
+
+    The band is the bins k with fmin <= freqs[k] <= fmax; ``fmin=None`` starts at bin 1 (DC is
+    under detrending what rounding left of a removed mean; ``fmin=0`` includes it), ``fmax=None``
+    ends at the last bin.  With the band's nb bins k_lo .. k_lo + nb - 1, returns ``(cnt, freqs,
+    B)``: ``freqs`` those nb frequencies and B complex128 (C, nb, nb) whatever ``axis`` was, (nb,
+    nb) for one-dimensional data,
+
+        B[c, a, b] = (1 / cnt) sum_s X[s, c, k1] X[s, c, k2] conj(X[s, c, k1 + k2]),
+        k1 = k_lo + a, k2 = k_lo + b
+
+    with the third factor read from the whole spectrum (k1 + k2 need not lie in the band) and no
+    one-sided doubling.  B is symmetric in (a, b) bit for bit (k2 <= k1 is computed, both mirrors
+    are written); entries with k1 + k2 > nfft // 2 lie outside the principal domain of a real
+    signal and are NaN, written and not computed.  Host data gives an ndarray, CUDA data a CUDA
+    tensor.
+
+    With ``detrend="constant"`` a non-finite sample in channel k makes channel k's entries NaN and
+    leaves every other channel's bits alone; ``detrend="linear"`` raises ``ValueError`` then.
+
+    Device memory: 32 B of sums per channel and band-bin pair (nb^2 of them: ``MemoryError``,
+    before anything is computed, when they or the result do not fit -- lower ``fmax`` or select
+    fewer channels), and per push the segment spectra and the plane |X| of at most ``max(1,
+    2**30 // (24 C nfreq))`` strides of samples per channel (about 1 GiB) -- it does not grow with
+    the stream.  Every sum is added in segment order, no atomics: the estimate does not depend on
+    how the stream is cut into chunks, and two calls give the same bits.
+    """
+    plan = _BispecPlan(fs, resolution, fmin, fmax, 16)
+    cnt, sums, power, host = _bispec_sums(plan, data, fs, axis, resolution, window, overlap, detrend, scaling)
+    B = dev.bispec_finish("spectrum", cnt, plan.k_lo, sums, power)
+    return cnt, plan.freqs, _bispec_result(B, host, plan.flat)
+
+
+def bicoherence(data, fs, method="kim", axis=-1, resolution=0.5, window="hann",
+                overlap=0.5, detrend="constant", fmin=None, fmax=None):
+    """Bicoherence of every channel: the bispectrum of ``bispectrum`` (same data, segments, band
+    and argument errors) normalised to [0, 1].  ``method`` is one name or a tuple of names; with
+    X1, X2, X3 = X[s, c, k1], X[s, c, k2], X[s, c, k1 + k2] and T = X1 X2 conj(X3):
+
+    ``"kim"``       |sum T|^2 / (sum |X1 X2|^2 sum |X3|^2), the squared bicoherence of Kim & Powers
+                    (1979); at most 1 by Cauchy-Schwarz;
+    ``"hagihira"``  |sum T| / sum |T|, the amplitude-normalised bicoherence (Hagihira et al. 2001);
+                    at most 1 by the triangle inequality, and kim <= hagihira^2.
+
+    The scaling cancels in both.  Returns ``(cnt, freqs, M)``: for one name M is float64 with the
+    shape of ``bispectrum``'s B, for a tuple a dict of name -> such an array in the order asked,
+    every measure from ONE pass over the stream and bit-identical to the single-name call.
+    Symmetric bit for bit, NaN outside the principal domain; a zero denominator gives what IEEE
+    gives.  Memory and reproducibility as for ``bispectrum``, plus 8 B per entry and measure.
+    """
+    names = _bicoherence_methods(method)
+    plan = _BispecPlan(fs, resolution, fmin, fmax, 8 * len(set(names)))
+    cnt, sums, power, host = _bispec_sums(plan, data, fs, axis, resolution, window, overlap, detrend, "density")
+    out = {}
+    for m in names:
+        if m not in out:
+            out[m] = _bispec_result(dev.bispec_finish(m, cnt, plan.k_lo, sums, power), host, plan.flat)
+    return cnt, plan.freqs, out[names[0]] if isinstance(method, str) else out
 
 
 def stft(data, fs, axis=-1, resolution=0.5, window="hann", overlap=0.5,
