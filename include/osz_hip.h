@@ -734,6 +734,47 @@ int osz_bispec_accumulate(const void *X, int64_t nseg, int nch, int nfreq, int k
 int osz_bispec_finish(int mode, const double *sums, const double *power, int64_t count, int nch, int nfreq,
                       int k_lo, int nb, void *out, void *stream);
 
+/* ---- time-resolved per-channel features (features/windowed.py window_features) ------------ */
+/* (csrc/windowfeat.hip, K15) */
+#define OSZ_WF_LONG 4096          /* windows of at least this many samples take a workgroup each, shorter ones a wave */
+#define OSZ_WF_LONGEST 134217728      /* the longest window, 2^27 samples: a window is addressed with 32-bit byte offsets  */
+typedef enum {                    /* dx_t = x_{t+1} - x_t, ddx_t = dx_{t+1} - dx_t, m_k the k-th central moment / W  */
+    OSZ_WF_MEAN = 0,
+    OSZ_WF_VAR = 1,               /* m_2                                                                 */
+    OSZ_WF_RMS = 2,               /* sqrt(mean x^2)                                                      */
+    OSZ_WF_SKEW = 3,              /* m_3 / m_2^1.5                                                       */
+    OSZ_WF_KURTOSIS = 4,          /* m_4 / m_2^2 (Pearson, not excess)                                   */
+    OSZ_WF_MIN = 5,
+    OSZ_WF_MAX = 6,
+    OSZ_WF_PTP = 7,               /* max - min                                                           */
+    OSZ_WF_LINE_LENGTH = 8,       /* sum |dx_t|                                                          */
+    OSZ_WF_ZERO_CROSSINGS = 9,    /* the number of t with (x_t < 0) != (x_{t+1} < 0)                     */
+    OSZ_WF_MOBILITY = 10,         /* sqrt(var(dx) / var(x))                                              */
+    OSZ_WF_COMPLEXITY = 11,       /* sqrt(var(ddx) / var(dx)) / mobility                                 */
+    OSZ_WF_TEAGER = 12,           /* mean over t = 1 .. W - 2 of x_t^2 - x_{t-1} x_{t+1}                 */
+    OSZ_WF_COUNT = 13
+} osz_window_feature;
+/*
+ * The windows of winsize samples, step apart, that n samples hold: 0 for n < winsize, else
+ * (n - winsize) / step + 1; -1 for n < 0, winsize < 4 or step < 1.  Touches no device.
+ */
+int64_t osz_window_count(int64_t n, int64_t winsize, int64_t step);
+/*
+ * x: nch rows of n f64 samples (device), row pitch `pitch` samples.  Window k of a row covers its
+ * samples k step .. k step + winsize - 1; for the nwin windows the n samples hold and every
+ * feature f whose bit 1 << f is set in mask (an osz_window_feature), in the order of the enum,
+ *   out[p * plane_pitch + c * row_pitch + win0 + k] = feature of window k of row c      (f64, device)
+ * with p the feature's rank among those present: successive pushes of a stream fill one result.
+ * Nothing else of out is touched.  A window that holds a NaN gives NaN in every feature; +-inf and
+ * a zero variance give what IEEE arithmetic gives from the definitions.  A window's bits depend
+ * on winsize and its own samples only -- not on step, the window's index, nch, mask or how the
+ * stream is cut into pushes: the partition of a window over lanes and the order of the fold are
+ * functions of winsize alone, and nothing is atomic.  winsize <= OSZ_WF_LONGEST.  One launch, no work space.
+ */
+int osz_window_features(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step,
+                        int mask, double *out, int64_t plane_pitch, int64_t row_pitch, int64_t win0,
+                        void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

@@ -35,6 +35,10 @@ ANALYTIC_GROUP = {"aec": ANALYTIC_AMP, "oaec": ANALYTIC_ORTH, "plv": ANALYTIC_LO
 ANALYTIC_PLANES = {ANALYTIC_AMP: 1, ANALYTIC_ORTH: 5, ANALYTIC_LOCK: 2, ANALYTIC_LAG: 2}
 ANALYTIC_BLOCK = 4096
 BISPEC_MODE = {"spectrum": 0, "kim": 1, "hagihira": 2}
+# OSZ_WF_*: a feature's bit in the mask of osz_window_features is 1 << its value
+WINDOW_FEATURE = {"mean": 0, "var": 1, "rms": 2, "skew": 3, "kurtosis": 4, "min": 5, "max": 6, "ptp": 7,
+                  "line_length": 8, "zero_crossings": 9, "mobility": 10, "complexity": 11, "teager": 12}
+WF_LONG = 4096       # OSZ_WF_LONG: windows of at least this many samples take the workgroup kernel
 
 
 class OszLibraryError(RuntimeError):
@@ -195,6 +199,9 @@ SIGNATURES = {
                                              c_vp, c_vp, c_vp, c_i64, c_vp]),
     "osz_bispec_finish": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, c_vp, c_vp]),
+    "osz_window_count": (c_i64, [c_i64, c_i64, c_i64]),
+    "osz_window_features": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, c_vp, c_i64,
+                                           c_i64, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),
