@@ -775,6 +775,41 @@ int osz_window_features(const double *x, int64_t pitch, int nch, int64_t n, int6
                         int mask, double *out, int64_t plane_pitch, int64_t row_pitch, int64_t win0,
                         void *stream);
 
+/* ---- sample and permutation entropy per window (features/entropy.py window_entropy) -------- */
+/* (csrc/windowent.hip, K16) */
+#define OSZ_WE_LONGEST 4096       /* the longest window: it is held in LDS, 32 KB                             */
+#define OSZ_WE_WIDE 512           /* windows of at least this many samples take 256 threads, shorter ones 64  */
+typedef enum {
+    OSZ_WE_SAMPLE = 0,            /* -ln(A / B), Richman & Moorman 2000                                   */
+    OSZ_WE_SAMPLE_A = 1,          /* A: template pairs i < j that match over m + 1 samples, as f64, exact */
+    OSZ_WE_SAMPLE_B = 2,          /* B: the pairs that match over m samples                               */
+    OSZ_WE_PERMUTATION = 3,       /* -sum p log2 p over the order! rank patterns, Bandt & Pompe 2002      */
+    OSZ_WE_COUNT = 4
+} osz_window_entropy_measure;
+enum { OSZ_WE_TOL_STD = 0, OSZ_WE_TOL_ABSOLUTE = 1 };
+/*
+ * x, the windows, mask (bit 1 << e of an osz_window_entropy_measure) and out are those of
+ * osz_window_features: out[p * plane_pitch + c * row_pitch + win0 + k], p the measure's rank among
+ * those present; nothing else of out is touched.  With x_0 .. x_{W-1} one window, W = winsize:
+ *   sample       the templates are i = 0 .. W - m - 1 for both lengths; B counts the pairs i < j
+ *                with max_{k < m} |x_{i+k} - x_{j+k}| <= rho, A the same with k <= m (<= in f64);
+ *                rho = r std(window) (divisor W, from sums about the window's first sample) for
+ *                OSZ_WE_TOL_STD, rho = r for OSZ_WE_TOL_ABSOLUTE.  A = 0 < B gives +inf, B = 0 NaN.
+ *   permutation  the vectors (x_t, x_{t+delay}, .., x_{t+(order-1) delay}), t = 0 .. W - 1 -
+ *                (order - 1) delay; the rank of element k is #{l : x_l < x_k} + #{l < k : x_l = x_k};
+ *                p the histogram of the order! patterns over the number of vectors; the result is
+ *                -sum p log2 p, over log2 order! when normalize is not 0.
+ * 4 <= winsize <= OSZ_WE_LONGEST, 1 <= m <= 8, r finite and >= 0, 2 <= order <= 6, delay >= 1;
+ * winsize >= m + 2 when a sample measure is asked, winsize > (order - 1) delay when permutation is.
+ * A window that holds a NaN or +-inf is NaN in every measure.  A window's bits depend on winsize,
+ * the parameters and its own samples only: the counts are integers, the sums for the std and the
+ * fold of the histogram run in an order that is a function of winsize alone, and no
+ * floating-point operation is atomic.  One launch, one workgroup per window, no work space.
+ */
+int osz_window_entropy(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step,
+                       int mask, int m, double r, int tolerance, int order, int64_t delay, int normalize,
+                       double *out, int64_t plane_pitch, int64_t row_pitch, int64_t win0, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

@@ -1467,3 +1467,37 @@ def window_features(x2d, winsize, step, mask, out, win0=0):
                                            int(step), int(mask), ptr(out), out.stride(0), out.stride(1), int(win0),
                                            stream_ptr()))
     return nwin
+
+
+def entropy_mask(names):
+    """The bit mask of osz_window_entropy for the measures ``names`` (keys of _lib.WINDOW_ENTROPY)."""
+    mask = 0
+    for name in names:
+        mask |= 1 << _lib.WINDOW_ENTROPY[name]
+    return mask
+
+
+def window_entropy(x2d, winsize, step, mask, m, r, tolerance, order, delay, normalize, out, win0=0):
+    """osz_window_entropy: the measures in the bit mask ``mask`` of every window of ``winsize``
+    samples, ``step`` apart, that x2d -- (nch, n) float64 CUDA rows, unit stride along n -- holds,
+    written to out[p, c, win0 + k]: out a contiguous float64 (planes, nch, room) CUDA tensor, one
+    plane per measure present in the order of _lib.WINDOW_ENTROPY.  ``tolerance`` is a key of
+    _lib.WE_TOLERANCE.  Returns the number of windows written per row."""
+    lib = require_gpu()
+    nch, n = x2d.shape
+    if x2d.dtype != torch.float64 or (n > 1 and x2d.stride(1) != 1) or (nch > 1 and x2d.stride(0) < n):
+        raise ValueError(f"window_entropy: x {tuple(x2d.shape)} {x2d.dtype} is not float64 (nch, n) rows")
+    planes = bin(int(mask)).count("1")
+    nwin = lib.osz_window_count(n, int(winsize), int(step))
+    if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_ENTROPY):
+        raise ValueError(f"window_entropy: bad sizes or measure mask ({n}, {winsize}, {step}, {mask})")
+    if (out.dtype != torch.float64 or out.ndim != 3 or out.shape[0] != planes or out.shape[1] != nch
+            or out.shape[2] < win0 + nwin or win0 < 0 or not out.is_contiguous()):
+        raise ValueError(f"window_entropy: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nch}, "
+                         f">= {win0 + nwin})")
+    if nwin:
+        _lib.check(lib.osz_window_entropy(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
+                                          int(step), int(mask), int(m), float(r), _lib.WE_TOLERANCE[tolerance],
+                                          int(order), int(delay), int(bool(normalize)), ptr(out), out.stride(0),
+                                          out.stride(1), int(win0), stream_ptr()))
+    return nwin

@@ -39,6 +39,11 @@ BISPEC_MODE = {"spectrum": 0, "kim": 1, "hagihira": 2}
 WINDOW_FEATURE = {"mean": 0, "var": 1, "rms": 2, "skew": 3, "kurtosis": 4, "min": 5, "max": 6, "ptp": 7,
                   "line_length": 8, "zero_crossings": 9, "mobility": 10, "complexity": 11, "teager": 12}
 WF_LONG = 4096       # OSZ_WF_LONG: windows of at least this many samples take the workgroup kernel
+# OSZ_WE_*: a measure's bit in the mask of osz_window_entropy is 1 << its value
+WINDOW_ENTROPY = {"sample": 0, "sample_a": 1, "sample_b": 2, "permutation": 3}
+WE_TOLERANCE = {"std": 0, "absolute": 1}      # OSZ_WE_TOL_*
+WE_LONGEST = 4096    # OSZ_WE_LONGEST: the longest window of osz_window_entropy (it is held in LDS)
+WE_WIDE = 512        # OSZ_WE_WIDE: windows of at least this many samples take a workgroup of 256, shorter ones a wave
 
 
 class OszLibraryError(RuntimeError):
@@ -202,6 +207,9 @@ SIGNATURES = {
     "osz_window_count": (c_i64, [c_i64, c_i64, c_i64]),
     "osz_window_features": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, c_vp, c_i64,
                                            c_i64, c_i64, c_vp]),
+    "osz_window_entropy": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_double, ctypes.c_int, ctypes.c_int, c_i64, ctypes.c_int, c_vp,
+                                          c_i64, c_i64, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

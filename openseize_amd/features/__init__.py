@@ -1,1 +1,2 @@
 from openseize_amd.features.windowed import WINDOW_FEATURES, window_features  # noqa: F401
+from openseize_amd.features.entropy import WINDOW_ENTROPIES, window_entropy  # noqa: F401
