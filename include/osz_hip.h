@@ -810,6 +810,42 @@ int osz_window_entropy(const double *x, int64_t pitch, int nch, int64_t n, int64
                        int mask, int m, double r, int tolerance, int order, int64_t delay, int normalize,
                        double *out, int64_t plane_pitch, int64_t row_pitch, int64_t win0, void *stream);
 
+/* ---- median, MAD and quantiles per window (features/quantiles.py window_quantiles) -------- */
+/* (csrc/windowquant.hip, K17) */
+#define OSZ_WQ_LONGEST 4096       /* the longest window: it is sorted on chip, 16 keys in each of 256 threads     */
+#define OSZ_WQ_QMOST 16           /* the most quantiles of one call: they travel in the kernel's arguments        */
+#define OSZ_WQ_NARROWEST 64       /* the least padded width; one kernel instance per power of two from here to    */
+                                  /* OSZ_WQ_LONGEST: a window is padded to the first of them that holds it         */
+#define OSZ_WQ_WAVE 512           /* windows of up to this many samples are sorted by one wave, longer ones by 256 threads */
+typedef enum {
+    OSZ_WQ_MEDIAN = 0,            /* the mean of the two middle samples of the sorted window (of the one) */
+    OSZ_WQ_MAD = 1,               /* the median of |x_t - median|, unscaled                               */
+    OSZ_WQ_QUANTILE = 2,          /* Hyndman & Fan type 7 for each of the nq values of q                  */
+    OSZ_WQ_COUNT = 3
+} osz_window_quantiles_measure;
+/*
+ * x, the windows, mask (bit 1 << e of an osz_window_quantiles_measure) and out are those of
+ * osz_window_features: out[p * plane_pitch + c * row_pitch + win0 + k]; the planes are, of those
+ * present in mask, median, mad and then the nq quantiles in the order of q; nothing else of out is
+ * touched.  q: nq values in [0, 1] in HOST memory (read only when OSZ_WQ_QUANTILE is asked, 1 <= nq
+ * <= OSZ_WQ_QMOST; any order, duplicates give duplicate planes).  With s_0 <= .. <= s_{W-1} the
+ * samples of one window, W = winsize, in ascending total order (-0.0 before +0.0: the order of
+ * the bits):
+ *   median    (s_{(W-1)/2} + s_{W/2}) / 2: one addition, one division.
+ *   quantile  h = p (W - 1), lo = floor(h), g = h - lo, hi = min(lo + 1, W - 1) -- computed here,
+ *             on the host, once; a = s_lo, b = s_hi; a where a == b, else with d = b - a
+ *             a + d g for g < 0.5 and b - d (1 - g) otherwise (numpy's linear method).
+ *   mad       the median, by the rule above, of |x_t - median| over the window.  NaN where the
+ *             median is not finite (inf - inf is among the deviations).
+ * Every operation is one IEEE operation, none contracted.  4 <= winsize <= OSZ_WQ_LONGEST.  A
+ * window that holds a NaN is NaN in every measure; +-inf are ordinary values of the sort.  A
+ * window's bits depend on winsize, q and its own samples only: the sort compares integer keys,
+ * and nothing is atomic.  One launch, one workgroup per window, no work space.
+ */
+int osz_window_quantiles(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step,
+                         int mask, const double *q, int nq, double *out, int64_t plane_pitch, int64_t row_pitch,
+                         int64_t win0, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

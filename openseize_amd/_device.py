@@ -1501,3 +1501,38 @@ def window_entropy(x2d, winsize, step, mask, m, r, tolerance, order, delay, norm
                                           int(order), int(delay), int(bool(normalize)), ptr(out), out.stride(0),
                                           out.stride(1), int(win0), stream_ptr()))
     return nwin
+
+
+def quantile_mask(names):
+    """The bit mask of osz_window_quantiles for the measures ``names`` (keys of _lib.WINDOW_QUANTILE)."""
+    mask = 0
+    for name in names:
+        mask |= 1 << _lib.WINDOW_QUANTILE[name]
+    return mask
+
+
+def window_quantiles(x2d, winsize, step, mask, q, out, win0=0):
+    """osz_window_quantiles: the measures in the bit mask ``mask`` of every window of ``winsize``
+    samples, ``step`` apart, that x2d -- (nch, n) float64 CUDA rows, unit stride along n -- holds,
+    written to out[p, c, win0 + k]: out a contiguous float64 (planes, nch, room) CUDA tensor whose
+    planes are, of those asked, median, mad and one per value of ``q`` (a sequence of floats, read
+    only with the quantile bit set).  Returns the number of windows written per row."""
+    lib = require_gpu()
+    nch, n = x2d.shape
+    if x2d.dtype != torch.float64 or (n > 1 and x2d.stride(1) != 1) or (nch > 1 and x2d.stride(0) < n):
+        raise ValueError(f"window_quantiles: x {tuple(x2d.shape)} {x2d.dtype} is not float64 (nch, n) rows")
+    nwin = lib.osz_window_count(n, int(winsize), int(step))
+    if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_QUANTILE):
+        raise ValueError(f"window_quantiles: bad sizes or measure mask ({n}, {winsize}, {step}, {mask})")
+    qs = [float(p) for p in q] if mask & (1 << _lib.WINDOW_QUANTILE["quantile"]) else []
+    planes = bin(int(mask) & 3).count("1") + len(qs)
+    if (out.dtype != torch.float64 or out.ndim != 3 or out.shape[0] != planes or out.shape[1] != nch
+            or out.shape[2] < win0 + nwin or win0 < 0 or not out.is_contiguous()):
+        raise ValueError(f"window_quantiles: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nch}, "
+                         f">= {win0 + nwin})")
+    if nwin:
+        qarr = (ctypes.c_double * max(len(qs), 1))(*qs)
+        _lib.check(lib.osz_window_quantiles(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
+                                            int(step), int(mask), ctypes.cast(qarr, ctypes.c_void_p), len(qs),
+                                            ptr(out), out.stride(0), out.stride(1), int(win0), stream_ptr()))
+    return nwin

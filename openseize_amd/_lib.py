@@ -44,6 +44,12 @@ WINDOW_ENTROPY = {"sample": 0, "sample_a": 1, "sample_b": 2, "permutation": 3}
 WE_TOLERANCE = {"std": 0, "absolute": 1}      # OSZ_WE_TOL_*
 WE_LONGEST = 4096    # OSZ_WE_LONGEST: the longest window of osz_window_entropy (it is held in LDS)
 WE_WIDE = 512        # OSZ_WE_WIDE: windows of at least this many samples take a workgroup of 256, shorter ones a wave
+# OSZ_WQ_*: a measure's bit in the mask of osz_window_quantiles is 1 << its value
+WINDOW_QUANTILE = {"median": 0, "mad": 1, "quantile": 2}
+WQ_LONGEST = 4096    # OSZ_WQ_LONGEST: the longest window of osz_window_quantiles (it is sorted on chip)
+WQ_QMOST = 16        # OSZ_WQ_QMOST: the most quantiles of one call
+WQ_NARROWEST = 64    # OSZ_WQ_NARROWEST: the least padded width; one kernel instance per power of two up to WQ_LONGEST
+WQ_WAVE = 512        # OSZ_WQ_WAVE: windows of up to this many samples are sorted by one wave, longer ones by 256 threads
 
 
 class OszLibraryError(RuntimeError):
@@ -210,6 +216,8 @@ SIGNATURES = {
     "osz_window_entropy": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_double, ctypes.c_int, ctypes.c_int, c_i64, ctypes.c_int, c_vp,
                                           c_i64, c_i64, c_i64, c_vp]),
+    "osz_window_quantiles": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, c_vp,
+                                            ctypes.c_int, c_vp, c_i64, c_i64, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

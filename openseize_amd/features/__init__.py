@@ -1,2 +1,3 @@
 from openseize_amd.features.windowed import WINDOW_FEATURES, window_features  # noqa: F401
 from openseize_amd.features.entropy import WINDOW_ENTROPIES, window_entropy  # noqa: F401
+from openseize_amd.features.quantiles import WINDOW_QUANTILES, window_quantiles  # noqa: F401
