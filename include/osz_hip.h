@@ -143,6 +143,42 @@ int osz_sosfiltfilt_step(osz_sos_t h, const double *x, int64_t ldx, int64_t nx,
                          int64_t na, const double *fb, int64_t ldfb, int64_t nb,
                          double *y, int64_t ldy, void *stream);
 
+/*
+ * What the handle's most recent osz_sos_forward, osz_sosfiltfilt_chunk or
+ * osz_sosfiltfilt_step call launched, in launch order: each launch site of the
+ * cascade notes what it launches, as it launches it.  A record is OSZ_SOS_LAUNCH_FIELDS
+ * int64 values:
+ *   [0] kernel      OSZ_SOSK_*
+ *   [1] rev         1 a backward pass, 0 a forward one, -1 one of each (the dual launches)
+ *   [2] guard       1 the bounds-checked body (a ragged length), 0 whole tiles
+ *   [3] al16        1 / 0 the instance for 16-byte aligned rows or the other; -1 the
+ *                   kernel has no such instances
+ *   [4] nseg        time segments per pass (1: one workgroup per channel)
+ *   [5] seglen      samples per segment but the last (the dual launches: of the
+ *                   forward pass; OSZ_SOSK_SEAL: of the runs it seals)
+ *   [6] seglen_b    the dual launches: samples per segment of the backward pass; else 0
+ *   [7] pre         samples segment s > 0 starts early, from a zero state
+ *   [8] prex        1 the chunk-local warm-up rides the launch as a pre-roll
+ *   [9] warmup      1 the state-only warm-up launch (nothing is written but a state)
+ *   [10] n          samples per channel (the dual launches: of the forward pass)
+ *   [11] n_b        the dual launches: samples per channel of the backward pass; else 0
+ * Up to `cap` records go to `out` (host, cap * OSZ_SOS_LAUNCH_FIELDS values); *count
+ * is the number of launches noted (at most OSZ_SOS_LAUNCH_RECORDS are kept).
+ */
+#define OSZ_SOS_LAUNCH_FIELDS 12
+#define OSZ_SOS_LAUNCH_RECORDS 8
+enum {
+    OSZ_SOSK_KERNEL = 0,      /* sos_kernel: one workgroup per channel           */
+    OSZ_SOSK_SPLIT = 1,       /* sos_split_kernel                                */
+    OSZ_SOSK_SPLIT_LEAN = 2,  /* sos_split_lean_kernel                           */
+    OSZ_SOSK_SPLIT2 = 3,      /* sos_split2_kernel                               */
+    OSZ_SOSK_DUAL = 4,        /* sos_dual_kernel                                 */
+    OSZ_SOSK_DUAL_LEAN = 5,   /* sos_dual_lean_kernel                            */
+    OSZ_SOSK_DUAL2 = 6,       /* sos_dual2_kernel                                */
+    OSZ_SOSK_SEAL = 7         /* sos_seal_kernel: NaN reach behind a cut forward pass */
+};
+int osz_sos_last_launches(osz_sos_t h, int64_t *out, int cap, int *count);
+
 /* ---- K1: streaming FFT overlap-add FIR -------------------------------- */
 /*
  * Replaces the np.fft.rfft / irfft circular convolution and overlap add of

@@ -651,6 +651,19 @@ class SosStream(_Handle):
         """Samples of the next chunk the backward warm-up reads (osz_sos_warm_len)."""
         return int(self.lib.osz_sos_warm_len(self.h))
 
+    def last_launches(self):
+        """What the most recent forward / backward / step launched, in launch order
+        (osz_sos_last_launches): one dict per launch, ``kernel`` by name."""
+        nf, cap = len(_lib.SOS_LAUNCH_FIELDS), _lib.SOS_LAUNCH_RECORDS
+        out, count = (ctypes.c_int64 * (nf * cap))(), ctypes.c_int(0)
+        _lib.check(self.lib.osz_sos_last_launches(self.h, out, cap, ctypes.byref(count)))
+        recs = []
+        for i in range(min(count.value, cap)):
+            r = dict(zip(_lib.SOS_LAUNCH_FIELDS, out[i * nf:(i + 1) * nf]))
+            r["kernel"] = _lib.SOS_KERNEL[r["kernel"]]
+            recs.append(r)
+        return recs
+
     def backward(self, fa, fb=None, out=None):
         """Chunk-local backward sweep (osz_sosfiltfilt_chunk)."""
         y = torch.empty_like(fa) if out is None else out

@@ -50,6 +50,12 @@ WQ_LONGEST = 4096    # OSZ_WQ_LONGEST: the longest window of osz_window_quantile
 WQ_QMOST = 16        # OSZ_WQ_QMOST: the most quantiles of one call
 WQ_NARROWEST = 64    # OSZ_WQ_NARROWEST: the least padded width; one kernel instance per power of two up to WQ_LONGEST
 WQ_WAVE = 512        # OSZ_WQ_WAVE: windows of up to this many samples are sorted by one wave, longer ones by 256 threads
+# OSZ_SOSK_*: the kernel of a record of osz_sos_last_launches, and the record's fields in order
+SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_dual", "sos_dual_lean",
+              "sos_dual2", "seal")
+SOS_LAUNCH_FIELDS = ("kernel", "rev", "guard", "al16", "nseg", "seglen", "seglen_b", "pre", "prex",
+                     "warmup", "n", "n_b")
+SOS_LAUNCH_RECORDS = 8
 
 
 class OszLibraryError(RuntimeError):
@@ -118,6 +124,8 @@ SIGNATURES = {
     "osz_chain_zp_seal": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
     "osz_chain_zp_finish": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp]),
     "osz_sos_warm_len": (c_i64, [c_vp]),
+    "osz_sos_last_launches": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_int)]),
     "osz_fir_create": (ctypes.c_int, [ctypes.POINTER(c_vp), c_dp, ctypes.c_int,
                                       ctypes.c_int]),
     "osz_fir_destroy": (ctypes.c_int, [c_vp]),

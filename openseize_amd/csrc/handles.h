@@ -41,8 +41,21 @@ struct osz_fir_s {
 };
 
 
+namespace osz {
+// what one launch site of the cascade launched (osz_sos_last_launches; the fields in
+// the order of include/osz_hip.h)
+struct SosLaunchRec {
+    int64_t kernel, rev, guard, al16, nseg, seglen, seglen_b, pre, prex, warmup, n, n_b;
+};
+struct SosLaunchLog {
+    int count;          // launches noted by the most recent call, the first 8 are kept
+    SosLaunchRec rec[8];    // OSZ_SOS_LAUNCH_RECORDS
+};
+}
+
 struct osz_sos_s {
     int device;         // HIP device the handle's buffers live on
+    osz::SosLaunchLog log;   // host side only: what the most recent call launched
     int T, NW;          // kernel geometry: samples per lane, waves per workgroup
     int64_t warm_len;   // samples of the sosfiltfilt warm-up that matter (see sos_warmup_len)
     int nsec, nch;
@@ -78,7 +91,8 @@ namespace osz {
 bool sos_nanfix();
 // NaN reach of a forward pass cut into runs (sos.hip): a small launch behind the pass
 int sos_seal_launch(double *y, int64_t ldy, int64_t n, int nseg, int64_t A, int64_t B, int64_t C, double *state,
-                    int nsec, int nch, double *carry, int64_t ldcarry, int64_t ncarry, hipStream_t st);
+                    int nsec, int nch, double *carry, int64_t ldcarry, int64_t ncarry, hipStream_t st,
+                    SosLaunchLog *log = nullptr);   // log: see sos_forward_raw
 // process-wide twiddle tables on the device (fir.hip)
 int get_fft_tables(fft::Tables &out);
 // per-section tables of a cascade for a tile of T samples per lane, built on
@@ -93,7 +107,7 @@ int sos_lane_table_for(osz_sos_s *h, int T, const double **dtab);
 // on two streams (sos.hip)
 int sosfiltfilt_chunk_on(osz_sos_s *h, const double *fa, int64_t ldfa, int64_t na, const double *fb,
                          int64_t ldfb, int64_t nb, double *y, int64_t ldy, double *tmp, double *carry,
-                         hipStream_t st);
+                         hipStream_t st, SosLaunchLog *log = nullptr);
 // ---- chain_spec.hip: FIR -> forward cascade in the spectrum.  While a pair of handles
 // runs it, their own states (overlap tail, section states) are not kept up to date:
 // every entry point that reads them calls spec_settle first, every one that changes
@@ -109,8 +123,9 @@ void spec_unlink(ChainSpec *s);
 // the entry points osz_fir_push / osz_sos_forward without those calls (fir.hip, sos.hip)
 int fir_push_raw(osz_fir_s *h, const double *x, int64_t ldx, int64_t n, double *y, int64_t ldy,
                  int64_t skip, hipStream_t st);
+// log: where the launches are noted (osz_sos_last_launches), null for callers it is not about
 int sos_forward_raw(osz_sos_s *h, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t n,
-                    hipStream_t st);
+                    hipStream_t st, SosLaunchLog *log = nullptr);
 // a backward pass over (nch, n) from the section states in `state` ((nsec, nch, 2), device);
 // the handle's own state is not touched (sos.hip)
 int sos_backward_raw(osz_sos_s *h, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t n,

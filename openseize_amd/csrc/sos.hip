@@ -849,6 +849,16 @@ static constexpr bool sos_pf() { return false; }
 // (sos_tile.h) -- A/B knob for tests/test_gpu_nonfinite.py, which fails with it
 bool sos_nanfix() { return true; }
 
+// osz_sos_last_launches: every launch site below notes what it launches, beside the
+// launch itself, in the log its caller hands down -- the handle's, from the three entry
+// points the log is about; null from every other caller (the chain kernels' steps).
+static_assert(sizeof(SosLaunchLog::rec) / sizeof(SosLaunchRec) == OSZ_SOS_LAUNCH_RECORDS &&
+              sizeof(SosLaunchRec) == OSZ_SOS_LAUNCH_FIELDS * sizeof(int64_t), "osz_hip.h");
+
+static void sos_note(SosLaunchLog *log, const SosLaunchRec &r) {
+    if (log && log->count < OSZ_SOS_LAUNCH_RECORDS) log->rec[log->count++] = r;
+}
+
 // NaN reach of a forward pass cut into runs (sos_tile.h): run q ends before sample
 // ((q + 1) A / B) C of the channel's row; from the first run whose last output is not finite
 // the rest of the row, the carried section states and / or a carried row become NaN.
@@ -886,10 +896,11 @@ __global__ void sos_seal_kernel(SealArgs g) {
 }
 
 int sos_seal_launch(double *y, int64_t ldy, int64_t n, int nseg, int64_t A, int64_t B, int64_t C, double *state,
-                    int nsec, int nch, double *carry, int64_t ldcarry, int64_t ncarry, hipStream_t st) {
+                    int nsec, int nch, double *carry, int64_t ldcarry, int64_t ncarry, hipStream_t st, SosLaunchLog *log) {
     if (!sos_nanfix() || nseg < 2 || !y) return OSZ_OK;
     SealArgs g{y, ldy, n, nseg, A, B, C, state, nsec, nch, carry, ldcarry, ncarry};
     hipLaunchKernelGGL(sos_seal_kernel, dim3(nch), dim3(nseg > 65 ? 256 : 64), 0, st, g);
+    sos_note(log, {OSZ_SOSK_SEAL, 0, 0, -1, nseg, (A / B) * C, 0, 0, 0, 0, n, 0});
     OSZ_HIP(hipGetLastError());
     return OSZ_OK;
 }
@@ -1096,7 +1107,7 @@ int sos_lane_table_for(osz_sos_s *h, int T, const double **dtab) {
 using namespace osz;
 
 template <int T, int NW, bool REV, bool GUARD>
-static int sos_launch_one(const SosArgs &a, hipStream_t st) {
+static int sos_launch_one(const SosArgs &a, hipStream_t st, SosLaunchLog *log) {
     auto kern = sos_kernel<T, NW, REV, GUARD>;
     const size_t lds = sizeof(double) * ((size_t)NW * 64 * (T + kSosPad) + 2 * NW * 2 +
                                          2 * kSosMaxSec * 2);
@@ -1105,6 +1116,7 @@ static int sos_launch_one(const SosArgs &a, hipStream_t st) {
         KernelTimer kt(REV ? (a.y ? (GUARD ? "sos_bwd_tail" : "sos_bwd") : "sos_warmup")
                            : (GUARD ? "sos_fwd_tail" : "sos_fwd"), st);
         hipLaunchKernelGGL(kern, dim3(a.nch), dim3(NW * 64), lds, st, a, a.sec);
+        sos_note(log, {OSZ_SOSK_KERNEL, REV, GUARD, -1, 1, a.n, 0, 0, a.prex != nullptr, REV && !a.y, a.n, 0});
     }
     OSZ_HIP(hipGetLastError());
     return OSZ_OK;
@@ -1138,11 +1150,11 @@ static int64_t sos_plan_segments(const SosArgs &a, int64_t tile, int64_t warm_le
 }
 
 template <int T, int NW, bool REV>
-static int sos_launch_main(const SosArgs &a, int64_t warm_len, hipStream_t st) {
+static int sos_launch_main(const SosArgs &a, int64_t warm_len, hipStream_t st, SosLaunchLog *log) {
     const int64_t tile = (int64_t)NW * 64 * T;
     const int64_t ntiles = a.n / tile;
     int64_t nseg = sos_plan_segments(a, tile, warm_len);
-    if (nseg <= 1) return sos_launch_one<T, NW, REV, false>(a, st);
+    if (nseg <= 1) return sos_launch_one<T, NW, REV, false>(a, st, log);
     const int64_t seg_tiles = (ntiles + nseg - 1) / nseg;
     nseg = (ntiles + seg_tiles - 1) / seg_tiles;
     const bool lean = sos_lean();
@@ -1159,11 +1171,13 @@ static int sos_launch_main(const SosArgs &a, int64_t warm_len, hipStream_t st) {
                 KernelTimer kt(REV ? (a.y ? "sos_bwd_split" : "sos_warmup") : "sos_fwd_split", st);
                 hipLaunchKernelGGL(k2, dim3(a.nch, (unsigned)nseg), dim3(NW * 64), lds2, st, a, a.sec,
                                    a.tab2, (int)nseg, seg_tiles * tile, warm_len);
+                sos_note(log, {OSZ_SOSK_SPLIT2, REV, 0, al, nseg, seg_tiles * tile, 0, warm_len, a.prex != nullptr,
+                          REV && !a.y, a.n, 0});
             }
             OSZ_HIP(hipGetLastError());
             if (!REV)
                 return sos_seal_launch(a.y, a.ldy, a.n, (int)nseg, 1, 1, seg_tiles * tile, a.state_out, a.nsec,
-                                       a.nch, nullptr, 0, 0, st);
+                                       a.nch, nullptr, 0, 0, st, log);
             return OSZ_OK;
         }
     }
@@ -1175,21 +1189,24 @@ static int sos_launch_main(const SosArgs &a, int64_t warm_len, hipStream_t st) {
         KernelTimer kt(REV ? (a.y ? "sos_bwd_split" : "sos_warmup") : "sos_fwd_split", st);
         hipLaunchKernelGGL(kern, dim3(a.nch, (unsigned)nseg), dim3(NW * 64), lds, st, a, a.sec,
                            (int)nseg, seg_tiles * tile, warm_len);
+        sos_note(log, {lean ? OSZ_SOSK_SPLIT_LEAN : OSZ_SOSK_SPLIT, REV, 0, -1, nseg, seg_tiles * tile, 0, warm_len,
+                  a.prex != nullptr, REV && !a.y, a.n, 0});
     }
     OSZ_HIP(hipGetLastError());
     if (!REV)
         return sos_seal_launch(a.y, a.ldy, a.n, (int)nseg, 1, 1, seg_tiles * tile, a.state_out, a.nsec, a.nch,
-                               nullptr, 0, 0, st);
+                               nullptr, 0, 0, st, log);
     return OSZ_OK;
 }
 
 template <int T, int NW, bool REV>
-static int sos_launch_tn(const SosArgs &a0, double *carry, int64_t warm_len, hipStream_t st) {
+static int sos_launch_tn(const SosArgs &a0, double *carry, int64_t warm_len, hipStream_t st,
+                         SosLaunchLog *log) {
     const int64_t tile = (int64_t)NW * 64 * T;
     const int64_t nfull = (a0.n / tile) * tile, rem = a0.n - nfull;
     if (nfull == 0 || rem == 0) {
-        return rem ? sos_launch_one<T, NW, REV, true>(a0, st)
-                   : sos_launch_main<T, NW, REV>(a0, warm_len, st);
+        return rem ? sos_launch_one<T, NW, REV, true>(a0, st, log)
+                   : sos_launch_main<T, NW, REV>(a0, warm_len, st, log);
     }
     SosArgs m = a0, r = a0;  // main (whole tiles) first in processing order, then remainder
     m.n = nfull;
@@ -1204,23 +1221,23 @@ static int sos_launch_tn(const SosArgs &a0, double *carry, int64_t warm_len, hip
     m.state_out = carry;
     r.state_in = carry;
     r.prex = nullptr;   // a pre-roll belongs to the launch that runs first
-    int rc = sos_launch_main<T, NW, REV>(m, warm_len, st);
+    int rc = sos_launch_main<T, NW, REV>(m, warm_len, st, log);
     if (rc) return rc;
-    return sos_launch_one<T, NW, REV, true>(r, st);
+    return sos_launch_one<T, NW, REV, true>(r, st, log);
 }
 
 template <bool REV>
 static int sos_launch(const SosArgs &a, double *carry, int T, int NW, int64_t warm_len,
-                      hipStream_t st) {
-    if (T == 32 && NW == 4) return sos_launch_tn<32, 4, REV>(a, carry, warm_len, st);
-    if (T == 32 && NW == 8) return sos_launch_tn<32, 8, REV>(a, carry, warm_len, st);
-    if (T == 16 && NW == 8) return sos_launch_tn<16, 8, REV>(a, carry, warm_len, st);
-    if (T == 16 && NW == 4) return sos_launch_tn<16, 4, REV>(a, carry, warm_len, st);
+                      hipStream_t st, SosLaunchLog *log) {
+    if (T == 32 && NW == 4) return sos_launch_tn<32, 4, REV>(a, carry, warm_len, st, log);
+    if (T == 32 && NW == 8) return sos_launch_tn<32, 8, REV>(a, carry, warm_len, st, log);
+    if (T == 16 && NW == 8) return sos_launch_tn<16, 8, REV>(a, carry, warm_len, st, log);
+    if (T == 16 && NW == 4) return sos_launch_tn<16, 4, REV>(a, carry, warm_len, st, log);
     return fail(OSZ_ERR_INVALID, "sos: unsupported geometry T=%d NW=%d", T, NW);
 }
 
 template <int T, int NW>
-static int sos_launch_dual(const SosArgs &f, const SosArgs &b, hipStream_t st) {
+static int sos_launch_dual(const SosArgs &f, const SosArgs &b, hipStream_t st, SosLaunchLog *log) {
     auto kern = sos_dual_kernel<T, NW>;
     const size_t lds = sizeof(double) * ((size_t)NW * 64 * (T + kSosPad) + 2 * NW * 2 +
                                          2 * kSosMaxSec * 2);
@@ -1228,6 +1245,7 @@ static int sos_launch_dual(const SosArgs &f, const SosArgs &b, hipStream_t st) {
     {
         KernelTimer kt("sos_dual", st);
         hipLaunchKernelGGL(kern, dim3(f.nch, 2), dim3(NW * 64), lds, st, f, b, f.sec);
+        sos_note(log, {OSZ_SOSK_DUAL, -1, 0, -1, 1, f.n, b.n, 0, b.prex != nullptr, 0, f.n, b.n});
     }
     OSZ_HIP(hipGetLastError());
     return OSZ_OK;
@@ -1236,7 +1254,7 @@ static int sos_launch_dual(const SosArgs &f, const SosArgs &b, hipStream_t st) {
 namespace osz {
 int sosfiltfilt_chunk_on(osz_sos_s *h, const double *fa, int64_t ldfa, int64_t na, const double *fb,
                          int64_t ldfb, int64_t nb, double *y, int64_t ldy, double *tmp, double *carry,
-                         hipStream_t st) {
+                         hipStream_t st, SosLaunchLog *log) {
     SosArgs a{};
     a.sec = h->dsec;
     a.nsec = h->nsec;
@@ -1277,7 +1295,7 @@ int sosfiltfilt_chunk_on(osz_sos_s *h, const double *fa, int64_t ldfa, int64_t n
         a.ldy = 0;
         a.state_in = nullptr;
         a.state_out = tmp;
-        int rc = sos_launch<true>(a, carry, h->T, h->NW, h->warm_len, st);
+        int rc = sos_launch<true>(a, carry, h->T, h->NW, h->warm_len, st, log);
         if (rc) return rc;
         a.state_in = tmp;
     } else {
@@ -1289,7 +1307,7 @@ int sosfiltfilt_chunk_on(osz_sos_s *h, const double *fa, int64_t ldfa, int64_t n
     a.y = y;
     a.ldy = ldy;
     a.state_out = nullptr;
-    return sos_launch<true>(a, carry, h->T, h->NW, h->warm_len, st);
+    return sos_launch<true>(a, carry, h->T, h->NW, h->warm_len, st, log);
 }
 }  // namespace osz
 
@@ -1384,6 +1402,14 @@ int osz_sos_set_zi_unit(osz_sos_t h, const double *zi_unit) {
 /* samples of the next chunk the chunk-local backward warm-up reads (1 << 62: all of it) */
 int64_t osz_sos_warm_len(osz_sos_t h) { return h ? h->warm_len : -1; }
 
+int osz_sos_last_launches(osz_sos_t h, int64_t *out, int cap, int *count) {
+    OSZ_REQUIRE(h && count && cap >= 0 && (out || cap == 0), "osz_sos_last_launches: bad argument");
+    *count = h->log.count;
+    const int k = h->log.count < cap ? h->log.count : cap;
+    if (k > 0) memcpy(out, h->log.rec, sizeof(SosLaunchRec) * (size_t)k);
+    return OSZ_OK;
+}
+
 int osz_sos_destroy(osz_sos_t h) {
     if (!h) return OSZ_OK;
     spec_unlink(h->spec);
@@ -1470,19 +1496,20 @@ int osz_sos_forward(osz_sos_t h, const double *x, int64_t ldx, double *y, int64_
     OSZ_REQUIRE(h && x && y, "osz_sos_forward: null argument");
     OSZ_REQUIRE(n >= 0 && ldx >= n && ldy >= n, "osz_sos_forward: n=%lld ldx=%lld ldy=%lld",
                 (long long)n, (long long)ldx, (long long)ldy);
+    h->log.count = 0;
     if (n == 0) return OSZ_OK;
     OSZ_SAME_DEVICE(h, "osz_sos_forward");
     {
         int rc = spec_touch(h->spec, as_stream(stream));
         if (rc) return rc;
     }
-    return sos_forward_raw(h, x, ldx, y, ldy, n, as_stream(stream));
+    return sos_forward_raw(h, x, ldx, y, ldy, n, as_stream(stream), &h->log);
 }
 
 }  // extern "C"
 
 int osz::sos_forward_raw(osz_sos_s *h, const double *x, int64_t ldx, double *y, int64_t ldy, int64_t n,
-                         hipStream_t st_) {
+                         hipStream_t st_, SosLaunchLog *log) {
     void *stream = st_;
     SosArgs a{};
     a.x = x;
@@ -1498,7 +1525,7 @@ int osz::sos_forward_raw(osz_sos_s *h, const double *x, int64_t ldx, double *y, 
     a.nch = h->nch;
     a.tab2 = h->dtab2;
     a.touch = h->touch;
-    int rc = sos_launch<false>(a, h->dcarry, h->T, h->NW, h->warm_len, as_stream(stream));
+    int rc = sos_launch<false>(a, h->dcarry, h->T, h->NW, h->warm_len, as_stream(stream), log);
     if (rc) return rc;
     std::swap(h->dstate, h->dstate_alt);
     return OSZ_OK;
@@ -1520,7 +1547,7 @@ int osz::sos_backward_raw(osz_sos_s *h, const double *x, int64_t ldx, double *y,
     a.nch = h->nch;
     a.tab2 = h->dtab2;
     a.touch = h->touch;
-    return sos_launch<true>(a, h->dcarry, h->T, h->NW, h->warm_len, st);
+    return sos_launch<true>(a, h->dcarry, h->T, h->NW, h->warm_len, st, nullptr);
 }
 
 extern "C" {
@@ -1534,6 +1561,8 @@ int osz_sosfiltfilt_step(osz_sos_t h, const double *x, int64_t ldx, int64_t nx, 
     OSZ_REQUIRE(na >= 1 && ldfa >= na && ldy >= na, "osz_sosfiltfilt_step: bad chunk a");
     OSZ_REQUIRE(!fb || (nb >= 1 && ldfb >= nb), "osz_sosfiltfilt_step: bad chunk b");
     OSZ_SAME_DEVICE(h, "osz_sosfiltfilt_step");
+    SosLaunchLog *log = &h->log;
+    log->count = 0;
     {
         int rc = spec_touch(h->spec, as_stream(stream));
         if (rc) return rc;
@@ -1542,9 +1571,11 @@ int osz_sosfiltfilt_step(osz_sos_t h, const double *x, int64_t ldx, int64_t nx, 
     const bool fusable = h->T == 32 && h->NW == 4 && nx % tile == 0 && na % tile == 0 &&
                          h->nch >= 96;   // fewer channels: time-split launches fill the chip better
     if (!fusable) {
-        int rc = osz_sos_forward(h, x, ldx, f, ldf, nx, stream);
+        // osz_sos_forward and osz_sosfiltfilt_chunk (their checks are made above), in one log
+        int rc = sos_forward_raw(h, x, ldx, f, ldf, nx, as_stream(stream), log);
         if (rc) return rc;
-        return osz_sosfiltfilt_chunk(h, fa, ldfa, na, fb, ldfb, nb, y, ldy, stream);
+        return sosfiltfilt_chunk_on(h, fa, ldfa, na, fb, ldfb, nb, y, ldy, h->dtmp, h->dcarry,
+                                    as_stream(stream), log);
     }
     hipStream_t st = as_stream(stream);
     SosArgs w{}, fw{}, bw{};
@@ -1571,7 +1602,7 @@ int osz_sosfiltfilt_step(osz_sos_t h, const double *x, int64_t ldx, int64_t nx, 
         w.ldx = ldfb;
         w.n = nb < h->warm_len ? nb : h->warm_len;
         w.state_out = h->dtmp;
-        int rc = sos_launch<true>(w, h->dcarry, h->T, h->NW, h->warm_len, st);
+        int rc = sos_launch<true>(w, h->dcarry, h->T, h->NW, h->warm_len, st, log);
         if (rc) return rc;
         bw.state_in = h->dtmp;
     }
@@ -1611,6 +1642,7 @@ int osz_sosfiltfilt_step(osz_sos_t h, const double *x, int64_t ldx, int64_t nx, 
                 KernelTimer kt("sos_dual", st);
                 hipLaunchKernelGGL(k2, dim3(h->nch, 2 * nseg), dim3(256), lds2, st, fw, bw, h->dsec,
                                    h->dtab2, nseg, sf, sb, h->warm_len);
+                sos_note(log, {OSZ_SOSK_DUAL2, -1, 0, al, nseg, sf, sb, h->warm_len, bw.prex != nullptr, 0, nx, na});
             } else {
                 auto kern = sos_dual_lean_kernel<32, 4>;
                 const size_t lds = sizeof(double) * ((size_t)4 * 32 * (32 + kSosPad) + 2 * 4 * 2 +
@@ -1619,11 +1651,12 @@ int osz_sosfiltfilt_step(osz_sos_t h, const double *x, int64_t ldx, int64_t nx, 
                 KernelTimer kt("sos_dual", st);
                 hipLaunchKernelGGL(kern, dim3(h->nch, 2 * nseg), dim3(256), lds, st, fw, bw,
                                    h->dsec, nseg, sf, sb, h->warm_len);
+                sos_note(log, {OSZ_SOSK_DUAL_LEAN, -1, 0, -1, nseg, sf, sb, h->warm_len, bw.prex != nullptr, 0, nx, na});
             }
             OSZ_HIP(hipGetLastError());
             {
                 int rcs = sos_seal_launch(fw.y, fw.ldy, fw.n, nseg, 1, 1, sf, fw.state_out, fw.nsec, fw.nch, nullptr,
-                                          0, 0, st);
+                                          0, 0, st, log);
                 if (rcs) return rcs;
             }
             std::swap(h->dstate, h->dstate_alt);
@@ -1635,12 +1668,12 @@ int osz_sosfiltfilt_step(osz_sos_t h, const double *x, int64_t ldx, int64_t nx, 
         w.ldx = ldfb;
         w.n = bw.npre;
         w.state_out = h->dtmp;
-        int rcw = sos_launch<true>(w, h->dcarry, h->T, h->NW, h->warm_len, st);
+        int rcw = sos_launch<true>(w, h->dcarry, h->T, h->NW, h->warm_len, st, log);
         if (rcw) return rcw;
         bw.state_in = h->dtmp;
         bw.prex = nullptr;
     }
-    int rc = sos_launch_dual<32, 4>(fw, bw, st);
+    int rc = sos_launch_dual<32, 4>(fw, bw, st, log);
     if (rc) return rc;
     std::swap(h->dstate, h->dstate_alt);
     return OSZ_OK;
@@ -1653,8 +1686,9 @@ int osz_sosfiltfilt_chunk(osz_sos_t h, const double *fa, int64_t ldfa, int64_t n
     OSZ_REQUIRE(na >= 1 && ldfa >= na && ldy >= na, "osz_sosfiltfilt_chunk: bad chunk a");
     OSZ_REQUIRE(!fb || (nb >= 1 && ldfb >= nb), "osz_sosfiltfilt_chunk: bad chunk b");
     OSZ_SAME_DEVICE(h, "osz_sosfiltfilt_chunk");
+    h->log.count = 0;
     return sosfiltfilt_chunk_on(h, fa, ldfa, na, fb, ldfb, nb, y, ldy, h->dtmp, h->dcarry,
-                                as_stream(stream));
+                                as_stream(stream), &h->log);
 }
 
 }  // extern "C"
