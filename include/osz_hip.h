@@ -418,6 +418,41 @@ int64_t osz_spec_seg_count(osz_spec_t h, int64_t n);
  * ignored and the handle's accumulator advances. */
 int osz_spec_push(osz_spec_t h, const double *x, int64_t ldx, int64_t n,
                   void *out, int64_t *nseg, void *stream);
+/*
+ * What the handle's most recent osz_spec_push launched, in launch order: each launch
+ * site of the engine notes what it launches, as it launches it (the small kernels
+ * that build the head buffer, fold partial sums and move the carry are not noted).
+ * Read-only.  A record is OSZ_SPEC_LAUNCH_FIELDS int64 values:
+ *   [0] family    OSZ_SPECK_*
+ *   [1] size      the instance's size parameter: N (cube, fft8), NT threads (mix,
+ *                 split), the convolution length M (blue); staged: nfft
+ *   [2] mode      osz_spec_mode
+ *   [3] linear    1 / 0: OSZ_DETREND_LINEAR or _CONSTANT
+ *   [4] half      cube, fft8: 1 / 0 the HALF instance (a pair shares a half); mix,
+ *                 split: the half-carry of the trend sums; -1: no such parameter
+ *   [5] nseg      segments of this launch (staged: of this batch)
+ *   [6] R         segments (mix, split) or segment pairs (cube, fft8, blue) per run,
+ *                 as the launch site planned it; staged: segments per batch
+ *   [7] nruns     runs per channel (staged: 1)
+ *   [8] head      1: the segments that begin in the carry, out of the head buffer;
+ *                 0: those inside the chunk; -1: one launch reads the carry itself
+ *   [9] npass     mix, split: passes of the radix plan; else 0
+ *   [10] R0, [11] S0   split: nfft / 2 = R0 S0; else 0
+ *   [12 ...]      radix[0 .. npass), zeros behind
+ * Up to `cap` records go to `out` (host, cap * OSZ_SPEC_LAUNCH_FIELDS values); *count
+ * is the number of launches noted (at most OSZ_SPEC_LAUNCH_RECORDS are kept).
+ */
+#define OSZ_SPEC_LAUNCH_FIELDS 26
+#define OSZ_SPEC_LAUNCH_RECORDS 8
+enum {
+    OSZ_SPECK_CUBE = 0,    /* spec_cube_kernel                       */
+    OSZ_SPECK_FFT8 = 1,    /* spec8_kernel                           */
+    OSZ_SPECK_MIX = 2,     /* specmix_kernel                         */
+    OSZ_SPECK_SPLIT = 3,   /* specsplit_kernel                       */
+    OSZ_SPECK_BLUE = 4,    /* spec_blue_kernel                       */
+    OSZ_SPECK_STAGED = 5   /* spec_prep_kernel, rocFFT, spec_post_kernel */
+};
+int osz_spec_last_launches(osz_spec_t h, int64_t *out, int cap, int *count);
 /* PSD_MEAN: raw sum of periodograms (nch, nfreq) f64 on the device and the
  * segment count so far -- a multi-GPU time split reduces these (RCCL) before
  * dividing.  The pointer stays owned by the handle. */

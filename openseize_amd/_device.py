@@ -944,6 +944,20 @@ class SpecStream(_Handle):
             stream_ptr()))
         return out
 
+    def last_launches(self):
+        """What the most recent push launched, in launch order (osz_spec_last_launches): one
+        dict per launch, ``family`` by name, ``radix`` the npass radices of a mix / split plan."""
+        nf, cap, ns = _lib.SPEC_LAUNCH_FIELDS, _lib.SPEC_LAUNCH_RECORDS, len(_lib.SPEC_LAUNCH_SCALARS)
+        out, count = (ctypes.c_int64 * (nf * cap))(), ctypes.c_int(0)
+        _lib.check(self.lib.osz_spec_last_launches(self.h, out, cap, ctypes.byref(count)))
+        recs = []
+        for i in range(min(count.value, cap)):
+            r = dict(zip(_lib.SPEC_LAUNCH_SCALARS, out[i * nf:i * nf + ns]))
+            r["family"] = _lib.SPEC_FAMILY[r["family"]]
+            r["radix"] = tuple(out[i * nf + ns:i * nf + ns + r["npass"]])
+            recs.append(r)
+        return recs
+
     def sum_tensor(self):
         """(device tensor view of the running periodogram sum, count)."""
         dsum, cnt = ctypes.c_void_p(), ctypes.c_int64()

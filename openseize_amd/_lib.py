@@ -56,6 +56,14 @@ SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_du
 SOS_LAUNCH_FIELDS = ("kernel", "rev", "guard", "al16", "nseg", "seglen", "seglen_b", "pre", "prex",
                      "warmup", "n", "n_b")
 SOS_LAUNCH_RECORDS = 8
+# OSZ_SPECK_*: the family of a record of osz_spec_last_launches, and the record's scalar fields in
+# order; SPEC_LAUNCH_RADIX values of the radix plan follow them
+SPEC_FAMILY = ("cube", "fft8", "mix", "split", "blue", "staged")
+SPEC_LAUNCH_SCALARS = ("family", "size", "mode", "linear", "half", "nseg", "R", "nruns", "head", "npass",
+                       "R0", "S0")
+SPEC_LAUNCH_RADIX = 14
+SPEC_LAUNCH_FIELDS = len(SPEC_LAUNCH_SCALARS) + SPEC_LAUNCH_RADIX
+SPEC_LAUNCH_RECORDS = 8
 
 
 class OszLibraryError(RuntimeError):
@@ -159,6 +167,8 @@ SIGNATURES = {
     "osz_spec_seg_count": (c_i64, [c_vp, c_i64]),
     "osz_spec_push": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp,
                                      ctypes.POINTER(c_i64), c_vp]),
+    "osz_spec_last_launches": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_int)]),
     "osz_spec_sum": (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp),
                                     ctypes.POINTER(c_i64)]),
     "osz_spec_export_sum": (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),

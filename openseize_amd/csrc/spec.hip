@@ -19,6 +19,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -1037,8 +1038,18 @@ int get_fft8_table(const double **out) {
 
 using namespace osz;
 
+// what one launch site of the spectra engine launched (osz_spec_last_launches; the fields in
+// the order of include/osz_hip.h)
+struct SpecLaunchRec {
+    int64_t family, size, mode, linear, half, nseg, R, nruns, head, npass, R0, S0;
+    int64_t radix[mix::kMaxPass];
+};
+static_assert(sizeof(SpecLaunchRec) == OSZ_SPEC_LAUNCH_FIELDS * sizeof(int64_t), "osz_hip.h");
+
 struct osz_spec_s {
     int device;         // HIP device the handle's buffers live on
+    int nlog;           // host side only: launches noted by the most recent push, the first 8 are kept
+    SpecLaunchRec log[OSZ_SPEC_LAUNCH_RECORDS];
     int nwin, nfft, stride, nfreq, detrend, mode, nch;
     double scale;
     double *dwindow;
@@ -1076,6 +1087,36 @@ struct osz_spec_s {
 };
 
 static const int64_t kSpecMaxElems = (int64_t)1 << 27;  // staging doubles per batch (1 GiB)
+
+// osz_spec_last_launches: every launch site below notes what it launches, beside the launch
+// itself.  half: -1 where the kernel has no such instances; head: -1 where one launch reads the
+// carry itself; the radix plan only for the mixed-radix and split kernels.
+static void spec_note(osz_spec_s *h, int family, int64_t size, int half, int64_t nseg, int64_t R,
+                      int64_t nruns, int head) {
+    if (h->nlog >= OSZ_SPEC_LAUNCH_RECORDS) {
+        ++h->nlog;
+        return;
+    }
+    SpecLaunchRec &r = h->log[h->nlog++];
+    r = SpecLaunchRec{};
+    r.family = family;
+    r.size = size;
+    r.mode = h->mode;
+    r.linear = h->detrend == OSZ_DETREND_LINEAR ? 1 : 0;
+    r.half = half;
+    r.nseg = nseg;
+    r.R = R;
+    r.nruns = nruns;
+    r.head = head;
+    if (family == OSZ_SPECK_MIX || family == OSZ_SPECK_SPLIT) {
+        r.npass = h->mix_npass;
+        for (int q = 0; q < h->mix_npass; ++q) r.radix[q] = h->mix_radix[q];
+    }
+    if (family == OSZ_SPECK_SPLIT) {
+        r.R0 = h->split_r0;
+        r.S0 = h->split_s0;
+    }
+}
 
 static int spec_plan(osz_spec_s *h, int64_t rows, rocfft_plan *out) {
     auto it = h->plans->find(rows);
@@ -1262,7 +1303,7 @@ static int specmix_launch_nt(osz_spec_s *h, const mix::Args &a, hipStream_t st) 
 
 // one launch of specmix_kernel over nseg segments of a contiguous source
 static int specmix_run(osz_spec_s *h, const double *src, int64_t ld, void *out, int64_t nseg,
-                       hipStream_t st) {
+                       int head, hipStream_t st) {
     int64_t R = (nseg * h->nch) / 2048;   // segments per run
     if (R > 64) R = 64;
     if (R < 1) R = 1;
@@ -1304,6 +1345,7 @@ static int specmix_run(osz_spec_s *h, const double *src, int64_t ld, void *out, 
         }
         a.partial = h->dpartial;
     }
+    spec_note(h, OSZ_SPECK_MIX, specmix_threads(a.M), a.halfcarry, nseg, R, nruns, head);
     int rc;
     switch (specmix_threads(a.M)) {
         case 64: rc = specmix_launch_nt<64>(h, a, st); break;
@@ -1363,7 +1405,7 @@ static int specsplit_launch_nt(osz_spec_s *h, const mix::SplitArgs &g, int64_t n
 
 // one launch of specsplit_kernel over nseg segments of a contiguous source
 static int specsplit_run(osz_spec_s *h, const double *src, int64_t ld, void *out, int64_t nseg,
-                         hipStream_t st) {
+                         int head, hipStream_t st) {
     const int R0 = h->split_r0, S0 = h->split_s0, NW = (R0 + 1) / 2, Ml = 2 * S0;     // the pairs and the self-paired
     // segments per run: long runs (a run's first segment sums both its halves) while a few
     // rounds of workgroups remain
@@ -1419,6 +1461,7 @@ static int specsplit_run(osz_spec_s *h, const double *src, int64_t ld, void *out
     }
     // workgroup ids: eight XCDs x (groups of units) x NW, specsplit.h
     const int64_t nblocks = ((int64_t)g.nunits + 7) / 8 * NW * 8;
+    spec_note(h, OSZ_SPECK_SPLIT, specmix_threads(Ml), a.halfcarry, nseg, R, nruns, head);
     int rc;
     switch (specmix_threads(Ml)) {
         case 256: rc = specsplit_launch_nt<256>(h, g, nblocks, st); break;
@@ -1523,7 +1566,8 @@ static int blue_launch(osz_spec_s *h, const BlueArgs &a, hipStream_t st) {
 }
 
 // one launch of spec_blue_kernel over nseg segments of a contiguous source
-static int blue_run(osz_spec_s *h, const double *src, int64_t ld, void *out, int64_t nseg, hipStream_t st) {
+static int blue_run(osz_spec_s *h, const double *src, int64_t ld, void *out, int64_t nseg, int head,
+                    hipStream_t st) {
     // pairs of segments per run: a few rounds of the chip, the set-up amortised
     const int64_t nitem = (nseg + 1) / 2;
     int64_t R = (nitem * h->nch) / 2048;
@@ -1558,6 +1602,7 @@ static int blue_run(osz_spec_s *h, const double *src, int64_t ld, void *out, int
         }
         a.partial = h->dpartial;
     }
+    spec_note(h, OSZ_SPECK_BLUE, h->blue_m, -1, nseg, R, nruns, head);
     int rc;
     switch (h->blue_m) {
         case 512: rc = blue_launch<512>(h, a, st); break;
@@ -1578,10 +1623,10 @@ static int blue_run(osz_spec_s *h, const double *src, int64_t ld, void *out, int
 
 // one launch of spec8_kernel over nseg segments of a contiguous source
 static int spec8_run(osz_spec_s *h, const double *src, int64_t ld, void *out, int64_t nseg,
-                     hipStream_t st) {
-    if (h->mixed) return specmix_run(h, src, ld, out, nseg, st);
-    if (h->split) return specsplit_run(h, src, ld, out, nseg, st);
-    if (h->blue) return blue_run(h, src, ld, out, nseg, st);
+                     int head, hipStream_t st) {
+    if (h->mixed) return specmix_run(h, src, ld, out, nseg, head, st);
+    if (h->split) return specsplit_run(h, src, ld, out, nseg, head, st);
+    if (h->blue) return blue_run(h, src, ld, out, nseg, head, st);
     const int64_t npairs = (nseg + 1) / 2;
     // runs: enough workgroups for a few rounds of the chip, long enough that the
     // per-run set-up (twiddles, window, partial sums) stays small
@@ -1613,6 +1658,8 @@ static int spec8_run(osz_spec_s *h, const double *src, int64_t ld, void *out, in
         }
         a.partial = h->dpartial;
     }
+    spec_note(h, OSZ_SPECK_FFT8, h->nfft, h->nwin == h->nfft && 2 * h->stride == h->nfft ? 1 : 0, nseg, R, nruns,
+              head);
     int rc;
     switch (h->nfft) {
         case 512: rc = spec8_launch<512>(h, a, st); break;
@@ -1655,14 +1702,14 @@ static int spec8_push(osz_spec_s *h, const double *x, int64_t ldx, int64_t n, vo
         hipLaunchKernelGGL(spec_head_kernel, dim3((unsigned)((h->ncarry + m + 255) / 256), h->nch), dim3(256),
                            0, st, h->dcarry[h->cur], h->ncap, h->ncarry, x, ldx, m, h->dhead, ldh);
         OSZ_HIP(hipGetLastError());
-        int rc = spec8_run(h, h->dhead, ldh, out, nhead, st);
+        int rc = spec8_run(h, h->dhead, ldh, out, nhead, 1, st);
         if (rc) return rc;
     }
     if (nseg > nhead) {
         // segment nhead starts at virtual sample nhead * stride >= ncarry
         const int64_t off = nhead * (int64_t)h->stride - h->ncarry;
         void *o = out ? (void *)((double *)out + (size_t)nhead * seg_out) : nullptr;
-        int rc = spec8_run(h, x + off, ldx, o, nseg - nhead, st);
+        int rc = spec8_run(h, x + off, ldx, o, nseg - nhead, 0, st);
         if (rc) return rc;
     }
     return OSZ_OK;
@@ -1683,6 +1730,7 @@ int osz_spec_create(osz_spec_t *h, int nwin, int nfft, int stride, const double 
     osz_spec_s *p = new osz_spec_s();
     p->device = 0;
     (void)hipGetDevice(&p->device);
+    p->nlog = 0;
     p->nwin = nwin;
     p->nfft = nfft;
     p->stride = stride;
@@ -1803,6 +1851,7 @@ int osz_spec_push(osz_spec_t h, const double *x, int64_t ldx, int64_t n, void *o
     OSZ_REQUIRE(n >= 0 && (n == 0 || (x && ldx >= n)), "osz_spec_push: bad input");
     OSZ_SAME_DEVICE(h, "osz_spec_push");
     hipStream_t st = as_stream(stream);
+    h->nlog = 0;
     const int64_t total = h->ncarry + n;
     const int64_t nseg = osz_spec_seg_count(h, n);
     OSZ_REQUIRE(nseg == 0 || h->mode == OSZ_SPEC_PSD_MEAN || out, "osz_spec_push: null output");
@@ -1858,6 +1907,7 @@ int osz_spec_push(osz_spec_t h, const double *x, int64_t ldx, int64_t n, void *o
         const kern_t ckern = ck[h->mode][h->detrend == OSZ_DETREND_LINEAR ? 1 : 0]
                                [h->stride == 2048 ? 1 : 0];
         OSZ_DYN_LDS(ckern, clds);
+        spec_note(h, OSZ_SPECK_CUBE, fft::N, h->stride == 2048 ? 1 : 0, nseg, R, nruns, -1);
         {
             KernelTimer kt("spec_fused", st);
             const dim3 grid((unsigned)nruns, h->nch), block(256);
@@ -1907,6 +1957,7 @@ int osz_spec_push(osz_spec_t h, const double *x, int64_t ldx, int64_t n, void *o
             pa.stride = h->stride;
             pa.nch = h->nch;
             pa.detrend = h->detrend;
+            spec_note(h, OSZ_SPECK_STAGED, h->nfft, -1, ns, segs_per_batch, 1, -1);   // one record per batch
             {
                 KernelTimer kt("spec_prep", st);
                 hipLaunchKernelGGL(spec_prep_kernel, dim3((unsigned)ns, h->nch), dim3(256), 0, st,
@@ -1971,6 +2022,15 @@ int osz_spec_push(osz_spec_t h, const double *x, int64_t ldx, int64_t n, void *o
         h->ncarry = nnew;
     }
     if (nseg_out) *nseg_out = nseg;
+    return OSZ_OK;
+}
+
+int osz_spec_last_launches(osz_spec_t h, int64_t *out, int cap, int *count) {
+    OSZ_REQUIRE(h && count && cap >= 0 && (out || cap == 0), "osz_spec_last_launches: bad argument");
+    const int kept = h->nlog < OSZ_SPEC_LAUNCH_RECORDS ? h->nlog : OSZ_SPEC_LAUNCH_RECORDS;
+    *count = h->nlog;
+    const int k = kept < cap ? kept : cap;
+    if (k > 0) memcpy(out, h->log, sizeof(SpecLaunchRec) * (size_t)k);
     return OSZ_OK;
 }
 

@@ -472,7 +472,8 @@ def test_stft_golden(osz, golden):
 def test_spectra_fused_4096(osz):
     """nfft = 4096 takes the fused on-chip path (pairs of segments per
     transform): check all three modes, both detrends, odd and even segment
-    counts and ragged pushes against the oracle and the rocFFT path."""
+    counts and ragged pushes against the oracle, the staged rocFFT route and the
+    fft8 kernel."""
     import os
     from oracle import oracle as orc
     from openseize_amd.spectra.estimators import psd, stft
@@ -497,14 +498,34 @@ def test_spectra_fused_4096(osz):
     f2, t2, X2 = orc.stft(x, fs, resolution=1.0, boundary=True, padded=True)
     assert X.shape == X2.shape and np.allclose(t, t2)
     assert np.max(np.abs(X - X2)) < RTOL * np.max(np.abs(X2))
-    # fused and rocFFT paths agree
-    os.environ["OSZ_SPEC_FUSED"] = "0"
-    try:
-        cnt0, _, p0 = psd(x, fs, axis=-1, resolution=1.0)
-    finally:
-        del os.environ["OSZ_SPEC_FUSED"]
-    cnt1, _, p1 = psd(x, fs, axis=-1, resolution=1.0)
+    # the cube, the fft8 kernel and the staged rocFFT route agree; which one a psd() took is
+    # read off its handle's launch report
+    from openseize_amd import _device as dev
+
+    def routed(**env):
+        seen, plain = set(), dev.SpecStream.push
+
+        def push(self, x2d):
+            out = plain(self, x2d)
+            seen.update(r["family"] for r in self.last_launches())
+            return out
+
+        os.environ.update(env)
+        dev.SpecStream.push = push
+        try:
+            cnt, _, p = psd(x, fs, axis=-1, resolution=1.0)
+        finally:
+            dev.SpecStream.push = plain
+            for k in env:
+                del os.environ[k]
+        return seen, cnt, p
+
+    fam1, cnt1, p1 = routed()
+    fam8, cnt8, p8 = routed(OSZ_SPEC_FUSED="0")
+    fam0, cnt0, p0 = routed(OSZ_SPEC_FUSED="0", OSZ_SPEC_V8="0", OSZ_SPEC_MIX="0")
+    assert (fam1, fam8, fam0) == ({"cube"}, {"fft8"}, {"staged"})
     assert cnt0 == cnt1 and rel_err(p1, p0) < 1e-12
+    assert cnt8 == cnt1 and rel_err(p1, p8) < 1e-12
 
 
 # ------------------------------------------- device-resident chain + masking
