@@ -917,6 +917,52 @@ int osz_window_quantiles(const double *x, int64_t pitch, int nch, int64_t n, int
                          int mask, const double *q, int nq, double *out, int64_t plane_pitch, int64_t row_pitch,
                          int64_t win0, void *stream);
 
+/* ---- spectral features per window (features/spectral.py window_spectral) ------------------ */
+/* (csrc/windowspec.hip, K18) */
+#define OSZ_WS_BANDS_MOST 16      /* the most bands of one call: they travel in the kernel's arguments            */
+#define OSZ_WS_EDGES_MOST 16      /* the most edge fractions of one call: they travel in the kernel's arguments   */
+#define OSZ_WS_WAVE 512           /* ranges of up to this many bins are reduced by one wave, longer ones by 256 threads */
+#define OSZ_WS_LDS 4096           /* ranges of up to this many bins are one tile and are read once; longer ones   */
+                                  /* are cut into tiles of this many bins and read twice, the second time from L2 */
+typedef enum {
+    OSZ_WS_TOTAL = 0,             /* df sum P_k: a rectangle sum (osz_simpson is the Simpson rule)              */
+    OSZ_WS_BAND = 1,              /* df sum of P_k over b0 <= k < b1, one plane per band                        */
+    OSZ_WS_RELATIVE = 2,          /* band / total, one plane per band                                           */
+    OSZ_WS_PEAK = 3,              /* f_k of the largest P_k, ties to the lowest k                               */
+    OSZ_WS_CENTROID = 4,          /* c = sum f_k P_k / sum P_k                                                  */
+    OSZ_WS_SPREAD = 5,            /* sqrt(sum (f_k - c)^2 P_k / sum P_k), the two-pass form                     */
+    OSZ_WS_EDGE = 6,              /* the lowest f_k whose cumulative sum reaches p sum P, one plane per p       */
+    OSZ_WS_ENTROPY = 7,           /* -sum p_k ln p_k, p_k = P_k / sum P; over ln n when normalize is set        */
+    OSZ_WS_FLATNESS = 8,          /* n exp(mean ln p_k): geometric over arithmetic mean; 0 where a p_k is 0     */
+    OSZ_WS_COUNT = 9
+} osz_window_spectral_feature;
+/*
+ * P: nrows = nseg * nch contiguous rows of nfreq float64 periodogram bins on the device, row
+ * s * nch + c that of segment s and channel c -- what an OSZ_SPEC_PSD_SEGMENTS push wrote.  One
+ * launch reduces the bins k0 .. k1 (inclusive; n = k1 - k0 + 1 of them) of every row to the
+ * features in mask (bit 1 << e of an osz_window_spectral_feature) and writes
+ * out[p * plane_pitch + c * row_pitch + win0 + s]; the planes are, of those present in mask and in
+ * the enum's order, total, nbands of band, nbands of relative, peak, centroid, spread, nedges of
+ * edge, entropy, flatness; nothing else of out is touched.  f_k = k * df, one multiply.  bands:
+ * nbands pairs of bins [b0, b1) in HOST memory, each not empty and inside k0 .. k1 + 1 (read only
+ * when BAND or RELATIVE is asked, 1 <= nbands <= OSZ_WS_BANDS_MOST; they may overlap).  edges:
+ * nedges fractions in (0, 1] in HOST memory (read only when EDGE is asked, 1 <= nedges <=
+ * OSZ_WS_EDGES_MOST); an edge is bin-valued, nothing is interpolated, and p = 1 gives a bin whose
+ * cumulative sum reaches the total (the last bin where rounding keeps every sum below it).  For n
+ * = 1 the entropy is 0.
+ * A row that holds a NaN in the range is NaN in every feature, peak and edge included.  A row
+ * whose range sums to exactly 0 gives total and band 0 and every other feature NaN.  A row's bits
+ * depend on its own bins k0 .. k1 and the arguments only -- not on nrows, the row's place, win0 or
+ * the other features in mask: every sum has an order that is a function of n alone, and the only
+ * atomic operation is an integer minimum.  Ranges of up to OSZ_WS_WAVE bins take one wave per row,
+ * longer ones 256 threads; up to OSZ_WS_LDS bins a row is read once, beyond that twice.  One
+ * launch, one workgroup per row, no work space.
+ */
+int osz_spectral_features(const double *P, int64_t nrows, int nch, int64_t nfreq, int64_t k0, int64_t k1,
+                          double df, const int *bands, int nbands, const double *edges, int nedges,
+                          int normalize, int mask, double *out, int64_t plane_pitch, int64_t row_pitch,
+                          int64_t win0, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

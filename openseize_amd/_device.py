@@ -1563,3 +1563,55 @@ def window_quantiles(x2d, winsize, step, mask, q, out, win0=0):
                                             int(step), int(mask), ctypes.cast(qarr, ctypes.c_void_p), len(qs),
                                             ptr(out), out.stride(0), out.stride(1), int(win0), stream_ptr()))
     return nwin
+
+
+def spectral_mask(names):
+    """The bit mask of osz_spectral_features for the features ``names`` (keys of _lib.WINDOW_SPECTRAL)."""
+    mask = 0
+    for name in names:
+        mask |= 1 << _lib.WINDOW_SPECTRAL[name]
+    return mask
+
+
+def spectral_planes(mask, nbands, nedges):
+    """The planes osz_spectral_features writes for ``mask``: one per feature, ``nbands`` for band and
+    for relative, ``nedges`` for edge."""
+    ws = _lib.WINDOW_SPECTRAL
+    return sum((nbands if name in ("band", "relative") else nedges if name == "edge" else 1)
+               for name, bit in ws.items() if mask & (1 << bit))
+
+
+def spectral_features(P, k0, k1, df, bands, edges, normalize, mask, out, win0=0):
+    """osz_spectral_features: the features in the bit mask ``mask`` of the bins k0 .. k1 (inclusive)
+    of every row of P -- a contiguous float64 (nseg, nch, nfreq) CUDA tensor of periodograms, what a
+    SPEC_PSD_SEGMENTS push returns -- written to out[p, c, win0 + s]: out a contiguous float64
+    (planes, nch, room) CUDA tensor whose planes are, of those asked and in the order of
+    _lib.WINDOW_SPECTRAL, total, one per band of band, one per band of relative, peak, centroid,
+    spread, one per fraction of edge, entropy, flatness.  ``bands``: pairs of bins (b0, b1), b1
+    exclusive, read only with the band or relative bit set; ``edges``: fractions in (0, 1], read
+    only with the edge bit set; f_k = k df.  Returns the number of segments written per channel."""
+    lib = require_gpu()
+    if P.dtype != torch.float64 or P.ndim != 3 or not P.is_contiguous():
+        raise ValueError(f"spectral_features: P {tuple(P.shape)} {P.dtype} is not contiguous float64 (nseg, nch, "
+                         "nfreq)")
+    nseg, nch, nfreq = P.shape
+    ws = _lib.WINDOW_SPECTRAL
+    if mask < 1 or mask >= 1 << len(ws) or not 0 <= k0 <= k1 < nfreq:
+        raise ValueError(f"spectral_features: bad feature mask or bin range ({mask}, {k0} .. {k1} of {nfreq})")
+    pairs = [(int(a), int(b)) for a, b in bands] if mask & (1 << ws["band"] | 1 << ws["relative"]) else []
+    fracs = [float(p) for p in edges] if mask & (1 << ws["edge"]) else []
+    planes = spectral_planes(mask, len(pairs), len(fracs))
+    if (out.dtype != torch.float64 or out.ndim != 3 or out.shape[0] != planes or out.shape[1] != nch
+            or out.shape[2] < win0 + nseg or win0 < 0 or not out.is_contiguous()):
+        raise ValueError(f"spectral_features: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nch}, "
+                         f">= {win0 + nseg})")
+    if nseg:
+        flat = [b for pair in pairs for b in pair]
+        barr = (ctypes.c_int * max(len(flat), 1))(*flat)
+        earr = (ctypes.c_double * max(len(fracs), 1))(*fracs)
+        _lib.check(lib.osz_spectral_features(ptr(P), nseg * nch, nch, nfreq, int(k0), int(k1), float(df),
+                                             ctypes.cast(barr, ctypes.c_void_p), len(pairs),
+                                             ctypes.cast(earr, ctypes.c_void_p), len(fracs), int(bool(normalize)),
+                                             int(mask), ptr(out), out.stride(0), out.stride(1), int(win0),
+                                             stream_ptr()))
+    return nseg

@@ -50,6 +50,13 @@ WQ_LONGEST = 4096    # OSZ_WQ_LONGEST: the longest window of osz_window_quantile
 WQ_QMOST = 16        # OSZ_WQ_QMOST: the most quantiles of one call
 WQ_NARROWEST = 64    # OSZ_WQ_NARROWEST: the least padded width; one kernel instance per power of two up to WQ_LONGEST
 WQ_WAVE = 512        # OSZ_WQ_WAVE: windows of up to this many samples are sorted by one wave, longer ones by 256 threads
+# OSZ_WS_*: a feature's bit in the mask of osz_spectral_features is 1 << its value
+WINDOW_SPECTRAL = {"total": 0, "band": 1, "relative": 2, "peak": 3, "centroid": 4, "spread": 5, "edge": 6,
+                   "entropy": 7, "flatness": 8}
+WS_BANDS_MOST = 16   # OSZ_WS_BANDS_MOST: the most bands of one call
+WS_EDGES_MOST = 16   # OSZ_WS_EDGES_MOST: the most edge fractions of one call
+WS_WAVE = 512        # OSZ_WS_WAVE: ranges of up to this many bins are reduced by one wave, longer ones by 256 threads
+WS_LDS = 4096        # OSZ_WS_LDS: ranges of up to this many bins are one tile, read once; longer ones are read twice
 # OSZ_SOSK_*: the kernel of a record of osz_sos_last_launches, and the record's fields in order
 SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_dual", "sos_dual_lean",
               "sos_dual2", "seal")
@@ -236,6 +243,9 @@ SIGNATURES = {
                                           c_i64, c_i64, c_i64, c_vp]),
     "osz_window_quantiles": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, c_vp,
                                             ctypes.c_int, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "osz_spectral_features": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_double, c_vp,
+                                             ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
+                                             c_i64, c_i64, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),
