@@ -963,6 +963,46 @@ int osz_spectral_features(const double *P, int64_t nrows, int nch, int64_t nfreq
                           int normalize, int mask, double *out, int64_t plane_pitch, int64_t row_pitch,
                           int64_t win0, void *stream);
 
+/* ---- channel-pair matrices per window (features/connectivity.py window_connectivity) ------ */
+/* (csrc/windowpair.hip, K19) */
+#define OSZ_WC_BLOCK 1024         /* a window's pair sums are chains over sub-blocks of this many samples counted */
+                                  /* from the window's start, folded in order                                      */
+typedef enum {
+    OSZ_WC_COV = 0,               /* real rows: numpy.cov of the window, divisor winsize - ddof                    */
+    OSZ_WC_CORR = 1,              /* real rows: numpy.corrcoef, clipped to [-1, 1]; diagonal 1.0                   */
+    OSZ_WC_AEC = 2,               /* complex rows: Pearson r of the envelopes |z|; diagonal 1.0                    */
+    OSZ_WC_PLV = 3,               /* complex rows: |s|, s = mean conj(u_i) u_j, u = z / |z|; diagonal 1.0          */
+    OSZ_WC_CIPLV = 4,             /* complex rows: |Im s| / sqrt(1 - (Re s)^2); diagonal 0.0                       */
+    OSZ_WC_COUNT = 5
+} osz_window_pair_measure;
+/*
+ * The float64 work space of one osz_window_pairs call with these arguments, in doubles: the staged
+ * planes |z|, u_x, u_y of complex data (3 nch n), two sums per (channel, window), and the Gram
+ * products of a batch of windows (at most 2^25 doubles, or one window's).  -1 for nch < 2 or >
+ * 16384, n < 0, winsize < 4, step < 1, an empty or unknown mask, or a mask that mixes the real
+ * measures (COV, CORR) with the complex ones or does not suit is_complex.  Touches no device.
+ */
+int64_t osz_window_pairs_work(int nch, int64_t n, int64_t winsize, int64_t step, int mask, int is_complex);
+/*
+ * x: nch rows of n samples on the device, row pitch `pitch` samples: float64 for is_complex = 0,
+ * complex128 (16-byte aligned) otherwise.  Window k covers the samples k step .. k step + winsize
+ * - 1 of every row; for the nwin = osz_window_count(n, winsize, step) windows and every measure m
+ * whose bit 1 << m is set in mask (an osz_window_pair_measure), in the order of the enum,
+ *   out[p * plane_pitch + (k * nch + i) * nch + j] = measure of rows i and j over window k   (f64)
+ * with p the measure's rank among those present.  Nothing else of out is touched.  ddof (0 or 1)
+ * enters COV alone.  [i, j] and [j, i] are written from one value.  An entry's bits depend on
+ * winsize, ddof and the window's samples of rows i and j only -- not on step, k, nch, the other
+ * rows, mask or how a stream is cut into pushes: the pair sums are the float64 MFMA's k-ordered
+ * chains over sub-blocks of OSZ_WC_BLOCK samples counted from the window's start, about the rows'
+ * first samples of the window, and nothing is atomic.  A row whose own sums over the window are
+ * not finite (a NaN or +-inf sample; for complex rows also a zero sample) is NaN in its row and
+ * column, the diagonal included; a constant real row gives COV exactly 0 and CORR NaN there.
+ * work: work_len >= osz_window_pairs_work(...) doubles on the device, the caller's.
+ */
+int osz_window_pairs(const void *x, int64_t pitch, int nch, int64_t n, int is_complex, int64_t winsize, int64_t step,
+                     int ddof, int mask, double *out, int64_t plane_pitch, double *work, int64_t work_len,
+                     void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

@@ -1615,3 +1615,40 @@ def spectral_features(P, k0, k1, df, bands, edges, normalize, mask, out, win0=0)
                                              int(mask), ptr(out), out.stride(0), out.stride(1), int(win0),
                                              stream_ptr()))
     return nseg
+
+
+def pair_mask(names):
+    """The bit mask of osz_window_pairs for the measures ``names`` (keys of _lib.WINDOW_CONNECTIVITY)."""
+    mask = 0
+    for name in names:
+        mask |= 1 << _lib.WINDOW_CONNECTIVITY[name]
+    return mask
+
+
+def window_pairs(x2d, winsize, step, ddof, mask, out):
+    """osz_window_pairs: the measures in the bit mask ``mask`` of every window of ``winsize``
+    samples, ``step`` apart, that x2d -- (nch, n) float64 (cov, corr) or complex128 (aec, plv,
+    ciplv) CUDA rows, unit stride along n -- holds, written to out[p, k, i, j]: out a contiguous
+    float64 (planes, nwin, nch, nch) CUDA tensor, one plane per measure present in the order of
+    _lib.WINDOW_CONNECTIVITY.  The work space is allocated here and freed on return.  Returns the
+    number of windows written."""
+    lib = require_gpu()
+    nch, n = x2d.shape
+    cplx = x2d.dtype == torch.complex128
+    if ((not cplx and x2d.dtype != torch.float64) or (n > 1 and x2d.stride(1) != 1)
+            or (nch > 1 and x2d.stride(0) < n)):
+        raise ValueError(f"window_pairs: x {tuple(x2d.shape)} {x2d.dtype} is not float64 or complex128 (nch, n) rows")
+    need = lib.osz_window_pairs_work(nch, n, int(winsize), int(step), int(mask), int(cplx))
+    if need < 0 or ddof not in (0, 1):
+        raise ValueError(f"window_pairs: bad sizes or measures for {x2d.dtype} data ({nch}, {n}, {winsize}, {step}, "
+                         f"{ddof}, {mask})")
+    nwin = lib.osz_window_count(n, int(winsize), int(step))
+    planes = bin(int(mask)).count("1")
+    if (out.dtype != torch.float64 or tuple(out.shape) != (planes, nwin, nch, nch) or not out.is_contiguous()):
+        raise ValueError(f"window_pairs: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nwin}, {nch}, "
+                         f"{nch})")
+    if nwin:
+        work = torch.empty(max(need, 1), dtype=torch.float64, device=x2d.device)
+        _lib.check(lib.osz_window_pairs(ptr(x2d), max(x2d.stride(0), n), nch, n, int(cplx), int(winsize), int(step),
+                                        int(ddof), int(mask), ptr(out), out.stride(0), ptr(work), need, stream_ptr()))
+    return nwin

@@ -57,6 +57,10 @@ WS_BANDS_MOST = 16   # OSZ_WS_BANDS_MOST: the most bands of one call
 WS_EDGES_MOST = 16   # OSZ_WS_EDGES_MOST: the most edge fractions of one call
 WS_WAVE = 512        # OSZ_WS_WAVE: ranges of up to this many bins are reduced by one wave, longer ones by 256 threads
 WS_LDS = 4096        # OSZ_WS_LDS: ranges of up to this many bins are one tile, read once; longer ones are read twice
+# OSZ_WC_*: a measure's bit in the mask of osz_window_pairs is 1 << its value; the first two take real data
+WINDOW_CONNECTIVITY = {"cov": 0, "corr": 1, "aec": 2, "plv": 3, "ciplv": 4}
+WC_REAL = ("cov", "corr")
+WC_BLOCK = 1024      # OSZ_WC_BLOCK: a window's pair sums are chains over sub-blocks of this many samples, folded in order
 # OSZ_SOSK_*: the kernel of a record of osz_sos_last_launches, and the record's fields in order
 SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_dual", "sos_dual_lean",
               "sos_dual2", "seal")
@@ -246,6 +250,9 @@ SIGNATURES = {
     "osz_spectral_features": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_double, c_vp,
                                              ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
                                              c_i64, c_i64, c_i64, c_vp]),
+    "osz_window_pairs_work": (c_i64, [ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int]),
+    "osz_window_pairs": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_int,
+                                        ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

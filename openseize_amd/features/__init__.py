@@ -2,3 +2,4 @@ from openseize_amd.features.windowed import WINDOW_FEATURES, window_features  # 
 from openseize_amd.features.entropy import WINDOW_ENTROPIES, window_entropy  # noqa: F401
 from openseize_amd.features.quantiles import WINDOW_QUANTILES, window_quantiles  # noqa: F401
 from openseize_amd.features.spectral import WINDOW_SPECTRAL, window_spectral  # noqa: F401
+from openseize_amd.features.connectivity import WINDOW_CONNECTIVITY, window_connectivity  # noqa: F401
