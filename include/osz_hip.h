@@ -205,6 +205,37 @@ int osz_fir_push(osz_fir_t h, const double *x, int64_t ldx, int64_t n,
  * Does not modify the carried tail. */
 int osz_fir_flush(osz_fir_t h, double *y, int64_t ldy, int64_t skip,
                   int64_t drop, void *stream);
+/*
+ * What the handle's most recent osz_fir_push launched, in launch order: one record per
+ * main-kernel launch, that is one per piece of the filter (one piece up to 2049 taps, pieces
+ * of 2048 taps beyond).  The seam kernel behind each launch and the work-row kernels of a
+ * partitioned filter are not noted.  A record is OSZ_FIR_LAUNCH_FIELDS int64 values:
+ *   [0] kernel      OSZ_FIRK_*
+ *   [1] rows        rows of 256 samples per block: NB of fir_nega_kernel<NB> (24 ... 31),
+ *                   NR of fir_oa_kernel<NR, 16, PF> (8 ... 15)
+ *   [2] pf          OSZ_FIRK_PAIR: the variant PF (fir_pf_table.h); OSZ_FIRK_NEGA: 0
+ *   [3] piece       index of the piece
+ *   [4] taps        taps of the piece
+ *   [5] step        samples per block, 256 rows
+ *   [6] nblocks     blocks of the push, the last one may be ragged
+ *   [7] R           the run length the planner aimed at, in blocks
+ *   [8] nruns       runs (workgroups per channel); run r starts at block
+ *                   min(2 floor(r ceil(nblocks / 2) / nruns), nblocks)
+ *   [9] accum       1 the launch adds into the work row of a partitioned filter, 0 it writes
+ *   [10] n          samples per channel
+ *   [11] skip       leading output samples not written (a piece of a partitioned filter: 0,
+ *                   the cut is made when the work row is drained)
+ * Up to `cap` records go to `out` (host, cap * OSZ_FIR_LAUNCH_FIELDS values); *count is the
+ * number of launches noted (at most OSZ_FIR_LAUNCH_RECORDS, one per piece, are kept).  A push
+ * of no samples launches nothing.
+ */
+#define OSZ_FIR_LAUNCH_FIELDS 12
+#define OSZ_FIR_LAUNCH_RECORDS 16
+enum {
+    OSZ_FIRK_NEGA = 0,        /* fir_nega_kernel: one real block per transform    */
+    OSZ_FIRK_PAIR = 1         /* fir_oa_kernel: a pair of blocks per transform    */
+};
+int osz_fir_last_launches(osz_fir_t h, int64_t *out, int cap, int *count);
 
 /* ---- K1 + K2 fused: FIR feeding the forward pass of a cascade --------- */
 /*

@@ -731,6 +731,19 @@ class FirStream(_Handle):
                                               drop, stream_ptr()))
         return y
 
+    def last_launches(self):
+        """What the most recent push launched, in launch order (osz_fir_last_launches): one
+        dict per main-kernel launch, that is per piece of the filter, ``kernel`` by name."""
+        nf, cap = len(_lib.FIR_LAUNCH_FIELDS), _lib.FIR_LAUNCH_RECORDS
+        out, count = (ctypes.c_int64 * (nf * cap))(), ctypes.c_int(0)
+        _lib.check(self.lib.osz_fir_last_launches(self.h, out, cap, ctypes.byref(count)))
+        recs = []
+        for i in range(min(count.value, cap)):
+            r = dict(zip(_lib.FIR_LAUNCH_FIELDS, out[i * nf:(i + 1) * nf]))
+            r["kernel"] = _lib.FIR_KERNEL[r["kernel"]]
+            recs.append(r)
+        return recs
+
 
 def chain_forward(fir, sos, x2d, out=None):
     """f = sosfilt(fir(x)) for the next chunk in one fused launch (C ABI:

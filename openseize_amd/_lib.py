@@ -67,6 +67,11 @@ SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_du
 SOS_LAUNCH_FIELDS = ("kernel", "rev", "guard", "al16", "nseg", "seglen", "seglen_b", "pre", "prex",
                      "warmup", "n", "n_b")
 SOS_LAUNCH_RECORDS = 8
+# OSZ_FIRK_*: the kernel of a record of osz_fir_last_launches, and the record's fields in order
+FIR_KERNEL = ("nega", "pair")
+FIR_LAUNCH_FIELDS = ("kernel", "rows", "pf", "piece", "taps", "step", "nblocks", "R", "nruns", "accum",
+                     "n", "skip")
+FIR_LAUNCH_RECORDS = 16
 # OSZ_SPECK_*: the family of a record of osz_spec_last_launches, and the record's scalar fields in
 # order; SPEC_LAUNCH_RADIX values of the radix plan follow them
 SPEC_FAMILY = ("cube", "fft8", "mix", "split", "blue", "staged")
@@ -155,6 +160,8 @@ SIGNATURES = {
     "osz_fir_push": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                     c_i64, c_vp]),
     "osz_fir_flush": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "osz_fir_last_launches": (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64), ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_int)]),
     "osz_poly_create": (ctypes.c_int, [ctypes.POINTER(c_vp), c_dp, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int]),

@@ -22,6 +22,7 @@
 //     samples) and written once (8 B): 16 B per channel-sample; the filter
 //     spectrum H (64 KB) and the twiddles live in registers for a whole run.
 #include <cmath>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -30,6 +31,7 @@
 #include "fft4096.h"
 #include "fir_pair.h"
 #include "fir_pf_table.h"
+#include "fir_plan.h"
 #include "handles.h"
 #include "nega_window.h"
 
@@ -351,13 +353,34 @@ int get_fft_tables(fft::Tables &out) {
 
 using namespace osz;
 
-constexpr int kFirPart = 2048;   // taps per piece of a partitioned filter
-constexpr int kFirMaxParts = 16; // => up to 32768 taps
+static_assert(kFirN == fft::N, "fir_plan.h");
+
+// osz_fir_last_launches: fir_part_push notes what it launches, beside the launch itself
+static_assert(sizeof(FirLaunchLog::rec) / sizeof(FirLaunchRec) == OSZ_FIR_LAUNCH_RECORDS &&
+              OSZ_FIR_LAUNCH_RECORDS == kFirMaxParts &&
+              sizeof(FirLaunchRec) == OSZ_FIR_LAUNCH_FIELDS * sizeof(int64_t), "osz_hip.h");
+
+static void fir_note(FirLaunchLog &log, const FirLaunchRec &r) {
+    if (log.count < OSZ_FIR_LAUNCH_RECORDS) log.rec[log.count++] = r;
+}
+
+// the device's compute units (fir_push_plan)
+static int fir_cus() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipGetDeviceProperties(&prop, dev) == hipSuccess)
+            cus = prop.multiProcessorCount;
+        if (cus <= 0) cus = 256;
+    }
+    return cus;
+}
 
 static int fir_build_part(FirPart &pt, const double *taps, int ntaps, int nch) {
     pt.ntaps = ntaps;
-    pt.step = ((fft::N - ntaps + 1) / 256) * 256;   // whole rows of 256: see fir_oa_kernel
-    if (pt.step > 15 * 256) pt.step = 15 * 256;
+    pt.step = fir_pair_step(ntaps);   // whole rows of 256: see fir_oa_kernel
     pt.cur = 0;
     pt.dH = pt.dstate[0] = pt.dstate[1] = nullptr;
     // H[k] = sum_m h[m] W4096^(k m) / 4096 in long double: an in-place radix-2
@@ -398,11 +421,8 @@ static int fir_build_part(FirPart &pt, const double *taps, int ntaps, int nch) {
     // taps twisted by e^{-i 2 pi m / 16384}, the same transform; stored in the order fft::cube2
     // leaves the bins in ([r][t])
     pt.dHn = nullptr;
-    pt.stepn = 0;
-    if (ntaps >= 2 && ntaps <= kFirMaxTaps) {
-        int nb = (2 * fft::N + 1 - ntaps) / 256;
-        if (nb > 31) nb = 31;
-        pt.stepn = 256 * nb;
+    pt.stepn = fir_nega_step(ntaps);
+    if (pt.stepn != 0) {
         std::fill(fr.begin(), fr.end(), 0.0L);
         std::fill(fi.begin(), fi.end(), 0.0L);
         for (int m = 0; m < ntaps; ++m) {
@@ -446,52 +466,14 @@ static int fir_build_part(FirPart &pt, const double *taps, int ntaps, int nch) {
 }
 
 // one overlap-add stream: main kernel + seam kernel
-static int fir_part_push(osz_fir_s *h, FirPart &pt, const double *x, int64_t ldx, int64_t n,
+static int fir_part_push(osz_fir_s *h, FirPart &pt, int piece, const double *x, int64_t ldx, int64_t n,
                          double *y, int64_t ldy, int64_t skip, int accum, hipStream_t st) {
     const int wm1 = pt.ntaps - 1;
-    // one real block per transform (fir_nega_kernel) where its tables exist
-    const bool nega = pt.dHn != nullptr && wm1 >= 1;
-    const int step = nega ? pt.stepn : pt.step;
-    const int64_t nblocks = (n + step - 1) / step;
-    // run length: long runs (every workgroup pays for its twiddle loads, its tail
-    // and its seam) as long as about 3/4 of the 512 workgroup slots stay busy --
-    // measured at 16..256 channels, runs of an even number of blocks
-    int64_t R = (nblocks * h->nch) / 384;
-    if (R > 32) R = 32;
-    if (R < 2) R = 2;
-    R &= ~1LL;
-    int64_t nruns = (nblocks + R - 1) / R;       // balanced runs of <= R blocks
-    {
-        // whole "rounds" of resident workgroups: with W workgroups on S slots the
-        // launch takes ceil(W / S) rounds, so prefer a run count that wastes
-        // little of the last round (slots = CUs x workgroups per CU by LDS)
-        static int cus = 0;
-        if (!cus) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess &&
-                hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                cus = prop.multiProcessorCount;
-            if (cus <= 0) cus = 256;
-        }
-        const int64_t slots = (int64_t)cus * 2;   // 64 KB of LDS per workgroup
-        int64_t best = nruns;
-        double best_waste = 2.0;
-        for (int64_t cand = nruns; cand < nruns + 8; ++cand) {
-            const int64_t w = cand * h->nch, rounds = (w + slots - 1) / slots;
-            const double waste = 1.0 - (double)w / (double)(rounds * slots);
-            if (waste < best_waste - 1e-9) {
-                best_waste = waste;
-                best = cand;
-            }
-        }
-        nruns = best;
-    }
-    // every run must hold at least one whole block (>= ntaps - 1 samples) so that
-    // tails never reach past the run that follows: at most one run per pair of
-    // blocks whose first block is whole
-    if (nruns > nblocks / 2) nruns = nblocks / 2;
-    if (nruns < 1) nruns = 1;
+    const FirPiecePlan pp = fir_piece_plan(pt.ntaps);
+    const bool nega = pp.nega != 0;
+    const int step = pp.step;
+    const FirPushPlan pl = fir_push_plan(n, step, h->nch, fir_cus());
+    const int64_t nblocks = pl.nblocks, R = pl.R, nruns = pl.nruns;
     const int64_t need = (int64_t)h->nch * nruns * (wm1 > 0 ? wm1 : 1);
     if (need > h->tails_cap) {
         // grow-only workspace; freeing waits for work that may still use it
@@ -525,8 +507,9 @@ static int fir_part_push(osz_fir_s *h, FirPart &pt, const double *x, int64_t ldx
         static const kern_t kn[8] = {fir_nega_kernel<24>, fir_nega_kernel<25>, fir_nega_kernel<26>,
                                      fir_nega_kernel<27>, fir_nega_kernel<28>, fir_nega_kernel<29>,
                                      fir_nega_kernel<30>, fir_nega_kernel<31>};
-        const int nb = step / 256;
+        const int nb = pp.rows;
         const size_t lds = sizeof(fft::cube::C2) * fft::cube::SLOTS + 1024;
+        fir_note(h->log, {OSZ_FIRK_NEGA, nb, 0, piece, pt.ntaps, step, nblocks, R, nruns, accum, n, skip});
         OSZ_DYN_LDS(kn[nb - 24], lds);
         KernelTimer kt("fir_oa", st);
         hipLaunchKernelGGL(kn[nb - 24], dim3((unsigned)nruns, h->nch), dim3(256), lds, st, a);
@@ -551,8 +534,9 @@ static int fir_part_push(osz_fir_s *h, FirPart &pt, const double *x, int64_t ldx
         // (benchmarks/check_async_regions.py on the assembly of THIS build;
         // tests/test_fir_async.py fails when the table and the assembly disagree).
         static const int kDefaultPf[8] = OSZ_FIR_PF_TABLE;
-        const int nr = pt.step / 256;
+        const int nr = pp.rows;
         const int pf = kDefaultPf[nr - 8];
+        fir_note(h->log, {OSZ_FIRK_PAIR, nr, pf, piece, pt.ntaps, step, nblocks, R, nruns, accum, n, skip});
         const kern_t *kerns = pf == 2 ? kerns2 : pf == 1 ? kerns1 : kerns0;
         size_t lds = sizeof(fft::cube::C2) * fft::cube::SLOTS;
         OSZ_DYN_LDS(kerns[nr - 8], lds);
@@ -591,7 +575,7 @@ int osz_fir_create(osz_fir_t *h, const double *taps, int ntaps, int nch) {
     OSZ_REQUIRE(h && taps, "osz_fir_create: null argument");
     OSZ_REQUIRE(nch >= 1 && nch <= 65535, "osz_fir_create: nch=%d not in [1, 65535]", nch);
     OSZ_REQUIRE(ntaps >= 1, "osz_fir_create: ntaps=%d must be positive", ntaps);
-    const int nparts = ntaps <= kFirMaxTaps ? 1 : (ntaps + kFirPart - 1) / kFirPart;
+    const int nparts = fir_nparts(ntaps);
     if (nparts > kFirMaxParts)
         return fail(OSZ_ERR_UNSUPPORTED, "osz_fir_create: %d taps > %d supported", ntaps,
                     kFirMaxParts * kFirPart);
@@ -606,12 +590,13 @@ int osz_fir_create(osz_fir_t *h, const double *taps, int ntaps, int nch) {
     p->htaps.assign(taps, taps + ntaps);
     p->tails_cap = p->w_cap = 0;
     p->dlen = 0;
+    p->log.count = 0;
     int rc = get_fft_tables(p->tb);
     if (rc) { delete p; return rc; }
     p->parts.resize(nparts);
     for (int q = 0; q < nparts; ++q) {
-        const int off = nparts == 1 ? 0 : q * kFirPart;
-        const int len = nparts == 1 ? ntaps : (ntaps - off < kFirPart ? ntaps - off : kFirPart);
+        const int off = fir_piece_off(nparts, q);
+        const int len = fir_piece_len(ntaps, nparts, q);
         rc = fir_build_part(p->parts[q], taps + off, len, nch);
         if (rc) {
             p->parts.resize(q + 1);   // the parts built so far (null pointers are fine to free)
@@ -717,12 +702,21 @@ int osz_fir_set_state(osz_fir_t h, const double *state, void *stream) {
     return fir_state_copy(h, const_cast<double *>(state), false, as_stream(stream));
 }
 
+int osz_fir_last_launches(osz_fir_t h, int64_t *out, int cap, int *count) {
+    OSZ_REQUIRE(h && count && cap >= 0 && (out || cap == 0), "osz_fir_last_launches: bad argument");
+    *count = h->log.count;
+    const int k = h->log.count < cap ? h->log.count : cap;
+    if (k > 0) memcpy(out, h->log.rec, sizeof(FirLaunchRec) * (size_t)k);
+    return OSZ_OK;
+}
+
 int osz_fir_push(osz_fir_t h, const double *x, int64_t ldx, int64_t n, double *y, int64_t ldy,
                  int64_t skip, void *stream) {
     OSZ_REQUIRE(h && x, "osz_fir_push: null argument");
     OSZ_REQUIRE(n >= 0 && ldx >= n, "osz_fir_push: n=%lld ldx=%lld", (long long)n, (long long)ldx);
     OSZ_REQUIRE(skip >= 0 && skip <= n, "osz_fir_push: skip=%lld not in [0, n]", (long long)skip);
     OSZ_REQUIRE(skip == n || (y && ldy >= n - skip), "osz_fir_push: bad output");
+    h->log.count = 0;
     if (n == 0) return OSZ_OK;
     OSZ_SAME_DEVICE(h, "osz_fir_push");
     {
@@ -736,8 +730,9 @@ int osz_fir_push(osz_fir_t h, const double *x, int64_t ldx, int64_t n, double *y
 
 int osz::fir_push_raw(osz_fir_s *h, const double *x, int64_t ldx, int64_t n, double *y, int64_t ldy,
                       int64_t skip, hipStream_t st) {
+    h->log.count = 0;
     if (h->parts.size() == 1)
-        return fir_part_push(h, h->parts[0], x, ldx, n, y, ldy, skip, 0, st);
+        return fir_part_push(h, h->parts[0], 0, x, ldx, n, y, ldy, skip, 0, st);
     // partitioned: accumulate every piece into W = [deferred | n new positions]
     const int64_t ldw = n + h->dlen;
     const int64_t need = (int64_t)h->nch * ldw;
@@ -757,8 +752,8 @@ int osz::fir_push_raw(osz_fir_s *h, const double *x, int64_t ldx, int64_t n, dou
                        h->dD, h->dlen);
     OSZ_HIP(hipGetLastError());
     for (size_t q = 0; q < h->parts.size(); ++q) {
-        int rc = fir_part_push(h, h->parts[q], x, ldx, n, h->dW + (int64_t)q * kFirPart, ldw, 0, 1,
-                               st);
+        int rc = fir_part_push(h, h->parts[q], (int)q, x, ldx, n, h->dW + (int64_t)q * kFirPart, ldw, 0,
+                               1, st);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(fir_w_drain_kernel, dim3((unsigned)bx, h->nch), dim3(256), 0, st, h->dW, ldw,

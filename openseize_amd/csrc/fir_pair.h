@@ -6,10 +6,9 @@
 
 #include "common.h"
 #include "fft4096.h"
+#include "fir_plan.h"   // kFirMaxTaps
 
 namespace osz {
-
-constexpr int kFirMaxTaps = 2049;  // NFFT - ntaps + 1 >= ntaps - 1
 
 struct FirArgs {
     const double *x;

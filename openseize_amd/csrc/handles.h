@@ -24,8 +24,21 @@ struct FirPart {
     int cur;
 };
 
+namespace osz {
+// what one main-kernel launch of a push launched (osz_fir_last_launches; the fields in the
+// order of include/osz_hip.h)
+struct FirLaunchRec {
+    int64_t kernel, rows, pf, piece, taps, step, nblocks, R, nruns, accum, n, skip;
+};
+struct FirLaunchLog {
+    int count;              // launches noted by the most recent push, the first 16 are kept
+    FirLaunchRec rec[16];   // OSZ_FIR_LAUNCH_RECORDS: one per piece
+};
+}
+
 struct osz_fir_s {
     int device;         // HIP device the handle's buffers live on
+    osz::FirLaunchLog log;   // host side only: what the most recent push launched
     int ntaps, nch;
     std::vector<FirPart> parts;
     double *dtails;     // run-tail workspace [nch][nruns_cap][<= 2048]

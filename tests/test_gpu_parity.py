@@ -159,10 +159,13 @@ def test_documented_divergences_are_exactly_these(osz, golden):
 
 
 def test_oaconvolve_every_block_height(osz):
-    """One filter length per compiled block height (8 ... 15 rows of 256 samples:
-    the whole-pair loop of fir_oa_kernel is a separate instantiation for each),
-    on runs long enough for the steady loop, several chunks (tail carried across
-    pushes, ragged last pair) and a partitioned filter (accumulating stores)."""
+    """One filter length in each of eight ranges of 200 taps, 1850 ... 2049 down to 58 ... 257:
+    fir_part_push sends every one of them to fir_nega_kernel, and they happen to land on its
+    eight block heights, NB = 24 ... 31 (8 ... 15 were the rows of fir_oa_kernel, which these
+    filters ran before fir_nega_kernel arrived; this test does not assert which instance
+    runs -- tests/test_gpu_fir_cells.py does, and reaches the runs of several whole blocks
+    that three channels never get here).  In one chunk and in several (tail carried across
+    pushes, ragged last block), and a partitioned filter (accumulating stores)."""
     from scipy.signal import oaconvolve as sp_oa
     rng = np.random.default_rng(77)
     x = rng.standard_normal((3, 150001))
