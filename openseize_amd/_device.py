@@ -1476,12 +1476,33 @@ def bispec_finish(mode, count, k_lo, sums, power):
     return out
 
 
-def window_mask(names):
-    """The bit mask of osz_window_features for the features ``names`` (keys of _lib.WINDOW_FEATURE)."""
+def name_mask(table, names):
+    """The bit mask a kernel takes for ``names``, keys of ``table``: one of _lib.WINDOW_FEATURE,
+    WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL and WINDOW_CONNECTIVITY, name -> bit."""
     mask = 0
     for name in names:
-        mask |= 1 << _lib.WINDOW_FEATURE[name]
+        mask |= 1 << table[name]
     return mask
+
+
+def _window_rows(who, x2d, complex_too=False):
+    """(nch, n) of ``x2d`` if it is (nch, n) float64 (``complex_too``: or complex128) rows with unit
+    stride along n and a pitch of n or more, else ``who``'s ValueError."""
+    nch, n = x2d.shape
+    kinds = (torch.float64, torch.complex128) if complex_too else (torch.float64,)
+    if x2d.dtype not in kinds or (n > 1 and x2d.stride(1) != 1) or (nch > 1 and x2d.stride(0) < n):
+        raise ValueError(f"{who}: x {tuple(x2d.shape)} {x2d.dtype} is not float64 "
+                         f"{'or complex128 ' if complex_too else ''}(nch, n) rows")
+    return nch, n
+
+
+def _window_out(who, out, planes, nch, nwin, win0):
+    """``who``'s ValueError unless ``out`` is contiguous float64 (planes, nch, room) with room for
+    ``nwin`` windows from ``win0`` on."""
+    if (out.dtype != torch.float64 or out.ndim != 3 or out.shape[0] != planes or out.shape[1] != nch
+            or out.shape[2] < win0 + nwin or win0 < 0 or not out.is_contiguous()):
+        raise ValueError(f"{who}: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nch}, "
+                         f">= {win0 + nwin})")
 
 
 def window_features(x2d, winsize, step, mask, out, win0=0):
@@ -1491,30 +1512,17 @@ def window_features(x2d, winsize, step, mask, out, win0=0):
     plane per feature present in the order of _lib.WINDOW_FEATURE.  Returns the number of windows
     written per row."""
     lib = require_gpu()
-    nch, n = x2d.shape
-    if x2d.dtype != torch.float64 or (n > 1 and x2d.stride(1) != 1) or (nch > 1 and x2d.stride(0) < n):
-        raise ValueError(f"window_features: x {tuple(x2d.shape)} {x2d.dtype} is not float64 (nch, n) rows")
+    nch, n = _window_rows("window_features", x2d)
     planes = bin(int(mask)).count("1")
     nwin = lib.osz_window_count(n, int(winsize), int(step))
     if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_FEATURE):
         raise ValueError(f"window_features: bad sizes or feature mask ({n}, {winsize}, {step}, {mask})")
-    if (out.dtype != torch.float64 or out.ndim != 3 or out.shape[0] != planes or out.shape[1] != nch
-            or out.shape[2] < win0 + nwin or win0 < 0 or not out.is_contiguous()):
-        raise ValueError(f"window_features: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nch}, "
-                         f">= {win0 + nwin})")
+    _window_out("window_features", out, planes, nch, nwin, win0)
     if nwin:
         _lib.check(lib.osz_window_features(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
                                            int(step), int(mask), ptr(out), out.stride(0), out.stride(1), int(win0),
                                            stream_ptr()))
     return nwin
-
-
-def entropy_mask(names):
-    """The bit mask of osz_window_entropy for the measures ``names`` (keys of _lib.WINDOW_ENTROPY)."""
-    mask = 0
-    for name in names:
-        mask |= 1 << _lib.WINDOW_ENTROPY[name]
-    return mask
 
 
 def window_entropy(x2d, winsize, step, mask, m, r, tolerance, order, delay, normalize, out, win0=0):
@@ -1524,31 +1532,18 @@ def window_entropy(x2d, winsize, step, mask, m, r, tolerance, order, delay, norm
     plane per measure present in the order of _lib.WINDOW_ENTROPY.  ``tolerance`` is a key of
     _lib.WE_TOLERANCE.  Returns the number of windows written per row."""
     lib = require_gpu()
-    nch, n = x2d.shape
-    if x2d.dtype != torch.float64 or (n > 1 and x2d.stride(1) != 1) or (nch > 1 and x2d.stride(0) < n):
-        raise ValueError(f"window_entropy: x {tuple(x2d.shape)} {x2d.dtype} is not float64 (nch, n) rows")
+    nch, n = _window_rows("window_entropy", x2d)
     planes = bin(int(mask)).count("1")
     nwin = lib.osz_window_count(n, int(winsize), int(step))
     if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_ENTROPY):
         raise ValueError(f"window_entropy: bad sizes or measure mask ({n}, {winsize}, {step}, {mask})")
-    if (out.dtype != torch.float64 or out.ndim != 3 or out.shape[0] != planes or out.shape[1] != nch
-            or out.shape[2] < win0 + nwin or win0 < 0 or not out.is_contiguous()):
-        raise ValueError(f"window_entropy: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nch}, "
-                         f">= {win0 + nwin})")
+    _window_out("window_entropy", out, planes, nch, nwin, win0)
     if nwin:
         _lib.check(lib.osz_window_entropy(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
                                           int(step), int(mask), int(m), float(r), _lib.WE_TOLERANCE[tolerance],
                                           int(order), int(delay), int(bool(normalize)), ptr(out), out.stride(0),
                                           out.stride(1), int(win0), stream_ptr()))
     return nwin
-
-
-def quantile_mask(names):
-    """The bit mask of osz_window_quantiles for the measures ``names`` (keys of _lib.WINDOW_QUANTILE)."""
-    mask = 0
-    for name in names:
-        mask |= 1 << _lib.WINDOW_QUANTILE[name]
-    return mask
 
 
 def window_quantiles(x2d, winsize, step, mask, q, out, win0=0):
@@ -1558,18 +1553,13 @@ def window_quantiles(x2d, winsize, step, mask, q, out, win0=0):
     planes are, of those asked, median, mad and one per value of ``q`` (a sequence of floats, read
     only with the quantile bit set).  Returns the number of windows written per row."""
     lib = require_gpu()
-    nch, n = x2d.shape
-    if x2d.dtype != torch.float64 or (n > 1 and x2d.stride(1) != 1) or (nch > 1 and x2d.stride(0) < n):
-        raise ValueError(f"window_quantiles: x {tuple(x2d.shape)} {x2d.dtype} is not float64 (nch, n) rows")
+    nch, n = _window_rows("window_quantiles", x2d)
     nwin = lib.osz_window_count(n, int(winsize), int(step))
     if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_QUANTILE):
         raise ValueError(f"window_quantiles: bad sizes or measure mask ({n}, {winsize}, {step}, {mask})")
     qs = [float(p) for p in q] if mask & (1 << _lib.WINDOW_QUANTILE["quantile"]) else []
     planes = bin(int(mask) & 3).count("1") + len(qs)
-    if (out.dtype != torch.float64 or out.ndim != 3 or out.shape[0] != planes or out.shape[1] != nch
-            or out.shape[2] < win0 + nwin or win0 < 0 or not out.is_contiguous()):
-        raise ValueError(f"window_quantiles: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nch}, "
-                         f">= {win0 + nwin})")
+    _window_out("window_quantiles", out, planes, nch, nwin, win0)
     if nwin:
         qarr = (ctypes.c_double * max(len(qs), 1))(*qs)
         _lib.check(lib.osz_window_quantiles(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
@@ -1579,11 +1569,10 @@ def window_quantiles(x2d, winsize, step, mask, q, out, win0=0):
 
 
 def spectral_mask(names):
-    """The bit mask of osz_spectral_features for the features ``names`` (keys of _lib.WINDOW_SPECTRAL)."""
-    mask = 0
-    for name in names:
-        mask |= 1 << _lib.WINDOW_SPECTRAL[name]
-    return mask
+    """``name_mask`` of _lib.WINDOW_SPECTRAL, under the name that the callers outside the package
+    know: tests/test_gpu_spectral.py and benchmarks/spectral_probe.py drive osz_spectral_features
+    through this module directly."""
+    return name_mask(_lib.WINDOW_SPECTRAL, names)
 
 
 def spectral_planes(mask, nbands, nedges):
@@ -1614,10 +1603,7 @@ def spectral_features(P, k0, k1, df, bands, edges, normalize, mask, out, win0=0)
     pairs = [(int(a), int(b)) for a, b in bands] if mask & (1 << ws["band"] | 1 << ws["relative"]) else []
     fracs = [float(p) for p in edges] if mask & (1 << ws["edge"]) else []
     planes = spectral_planes(mask, len(pairs), len(fracs))
-    if (out.dtype != torch.float64 or out.ndim != 3 or out.shape[0] != planes or out.shape[1] != nch
-            or out.shape[2] < win0 + nseg or win0 < 0 or not out.is_contiguous()):
-        raise ValueError(f"spectral_features: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nch}, "
-                         f">= {win0 + nseg})")
+    _window_out("spectral_features", out, planes, nch, nseg, win0)
     if nseg:
         flat = [b for pair in pairs for b in pair]
         barr = (ctypes.c_int * max(len(flat), 1))(*flat)
@@ -1630,14 +1616,6 @@ def spectral_features(P, k0, k1, df, bands, edges, normalize, mask, out, win0=0)
     return nseg
 
 
-def pair_mask(names):
-    """The bit mask of osz_window_pairs for the measures ``names`` (keys of _lib.WINDOW_CONNECTIVITY)."""
-    mask = 0
-    for name in names:
-        mask |= 1 << _lib.WINDOW_CONNECTIVITY[name]
-    return mask
-
-
 def window_pairs(x2d, winsize, step, ddof, mask, out):
     """osz_window_pairs: the measures in the bit mask ``mask`` of every window of ``winsize``
     samples, ``step`` apart, that x2d -- (nch, n) float64 (cov, corr) or complex128 (aec, plv,
@@ -1646,11 +1624,8 @@ def window_pairs(x2d, winsize, step, ddof, mask, out):
     _lib.WINDOW_CONNECTIVITY.  The work space is allocated here and freed on return.  Returns the
     number of windows written."""
     lib = require_gpu()
-    nch, n = x2d.shape
+    nch, n = _window_rows("window_pairs", x2d, complex_too=True)
     cplx = x2d.dtype == torch.complex128
-    if ((not cplx and x2d.dtype != torch.float64) or (n > 1 and x2d.stride(1) != 1)
-            or (nch > 1 and x2d.stride(0) < n)):
-        raise ValueError(f"window_pairs: x {tuple(x2d.shape)} {x2d.dtype} is not float64 or complex128 (nch, n) rows")
     need = lib.osz_window_pairs_work(nch, n, int(winsize), int(step), int(mask), int(cplx))
     if need < 0 or ddof not in (0, 1):
         raise ValueError(f"window_pairs: bad sizes or measures for {x2d.dtype} data ({nch}, {n}, {winsize}, {step}, "

@@ -6,36 +6,17 @@ window, from one pass over the stream.  The pair sums are Gram products with tim
 dimension and run on the float64 matrix pipe: ``csrc/windowpair.hip`` (K19), ``osz_window_pairs``.
 """
 
+import functools
+
 import numpy as np
 
 from openseize_amd import _device as dev
 from openseize_amd import _lib
-from openseize_amd.core.producer import Producer, producer
-from openseize_amd.features.windowed import _PUSH_BYTES, _advance, window_count, window_plan  # noqa: F401
+from openseize_amd.features import _stream
+from openseize_amd.features._stream import _advance, window_count, window_plan  # noqa: F401  (the family's)
 
 WINDOW_CONNECTIVITY = tuple(_lib.WINDOW_CONNECTIVITY)
 _REAL = _lib.WC_REAL
-
-
-def _names(measures):
-    names = (measures,) if isinstance(measures, str) or not isinstance(measures, (tuple, list)) else tuple(measures)
-    bad = [m for m in names if not isinstance(m, str) or m not in WINDOW_CONNECTIVITY]
-    if bad or not names:
-        raise ValueError(f"unknown window connectivity measure(s) {bad}: choose from {WINDOW_CONNECTIVITY}")
-    if len({m in _REAL for m in names}) > 1:
-        raise ValueError(f"window_connectivity: {_REAL} take real data and the other measures of {WINDOW_CONNECTIVITY} "
-                         f"complex (analytic) data: {names} cannot come from one stream")
-    return names
-
-
-def _size(value, least, what):
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least:
-        raise ValueError(f"window_connectivity: {what} must be an integer >= {least}, got {value!r}")
-    return int(value)
-
-
-def _is_complex(arr):
-    return arr.is_complex() if dev.is_tensor(arr) else np.iscomplexobj(arr)
 
 
 def _kind(names, is_complex, what):
@@ -106,64 +87,35 @@ def window_connectivity(data, winsize, step=None, measures=("corr",), ddof=1, ax
     CUDA-fed results stay on the device: when the 8 P C^2 nwin bytes of P measures do not fit the
     free device memory, ``MemoryError`` is raised before anything runs.
     """
-    names = _names(measures)
-    W = _size(winsize, 4, "winsize")
-    step = W if step is None else _size(step, 1, "step")
+    who = "window_connectivity"
+    names = _stream._names(measures, WINDOW_CONNECTIVITY, "window connectivity measure(s)")
+    if len({m in _REAL for m in names}) > 1:
+        raise ValueError(f"window_connectivity: {_REAL} take real data and the other measures of {WINDOW_CONNECTIVITY} "
+                         f"complex (analytic) data: {names} cannot come from one stream")
+    W = _stream._size(winsize, 4, None, who, "winsize")
+    step = W if step is None else _stream._size(step, 1, None, who, "step")
     if isinstance(ddof, bool) or ddof not in (0, 1):
         raise ValueError(f"window_connectivity: ddof must be 0 or 1, got {ddof!r}")
-    if isinstance(data, Producer):
-        pro = producer(data, data.chunksize, axis)
-    else:
-        if dev.is_arraylike(data):
-            _kind(names, _is_complex(data), f"{data.dtype} data")
-        pro = producer(data, int(10e6) if chunksize is None else chunksize, axis)
-    if len(pro.shape) != 2:
-        raise ValueError(f"window_connectivity needs two-dimensional data (channels x samples), got shape "
-                         f"{tuple(pro.shape)}: "
-                         + ("stack at least two channels" if len(pro.shape) < 2 else "reshape the channel axes into one"))
-    layout = dev.Layout(pro.shape, axis)
-    nch, nsamp = layout.nch, pro.shape[layout.axis]
-    if nch < 2:
-        raise ValueError(f"window_connectivity needs at least two channels, got shape {tuple(pro.shape)}")
-    if nsamp < W:
-        raise ValueError(f"window_connectivity: the stream holds {nsamp} samples, fewer than one window of {W}")
+    kind = functools.partial(_kind, names)
+    pro, layout = _stream._open(who, data, axis, chunksize, W, kind, pairs=True)
+    nch = layout.nch
     is_complex = names[0] not in _REAL
-    order = [m for m in WINDOW_CONNECTIVITY if m in names]    # the planes a push writes
-    mask = dev.pair_mask(order)
-    host = dev.origin_is_host(pro)
+    order = [m for m in WINDOW_CONNECTIVITY if m in names]    # the planes a launch writes
+    mask = dev.name_mask(_lib.WINDOW_CONNECTIVITY, order)
+    expect = window_count(pro.shape[layout.axis], W, step)
+    need = 8 * len(order) * nch * nch * expect
     torch = dev.torch
-    most = max(1, _PUSH_BYTES // (8 * len(order) * nch * nch))    # windows per launch
-    parts, carry, skip, total, started = [], None, 0, 0, False
-    for arr in dev.pull_resident(pro, pro):
-        _kind(names, _is_complex(arr), f"{arr.dtype} chunks")
-        if not started:
-            dev.require_gpu()
-        x2d, was_host = _rows(arr, layout, is_complex)
-        host = host or was_host
-        if not started:
-            started = True
-            need = 8 * len(order) * nch * nch * window_count(nsamp, W, step)
-            if not host and need > torch.cuda.mem_get_info()[0]:
-                raise MemoryError(f"window_connectivity: the {len(order)} x ({window_count(nsamp, W, step)}, {nch}, "
-                                  f"{nch}) float64 results need {need / 1e9:.2f} GB, more than the "
-                                  f"{torch.cuda.mem_get_info()[0] / 1e9:.2f} GB of device memory that are free: "
-                                  f"raise step (now {step}; winsize {W}) or select fewer of the {nch} channels")
-        have = 0 if carry is None else carry.shape[1]
-        drop, nwin, keep, skip = _advance(have, skip, x2d.shape[1], W, step)
-        if drop:
-            x2d = x2d[:, drop:]
-        if carry is not None:
-            x2d = torch.cat((carry, x2d), dim=1)
-        for k0 in range(0, nwin, most):
-            k1 = min(k0 + most, nwin)
-            out = torch.empty((len(order), k1 - k0, nch, nch), dtype=torch.float64, device=x2d.device)
-            dev.window_pairs(x2d[:, k0 * step:(k1 - 1) * step + W], W, step, ddof, mask, out)
-            parts.append(out.cpu().numpy() if host else out)
-        total += nwin
-        # (a copy: a source may fill the chunk's memory again before the next push reads it)
-        carry = x2d[:, x2d.shape[1] - keep:].clone() if keep else None
-    if total == 0:
-        raise ValueError(f"window_connectivity: the stream ended before one window of {W} samples was full")
+    parts, host = [], None
+    for x, n, host in _stream._launches(who, pro, W, step, kind, lambda arr: _rows(arr, layout, is_complex),
+                                        8 * len(order) * nch * nch):
+        if not parts and not host and need > torch.cuda.mem_get_info()[0]:      # (before the first launch)
+            raise MemoryError(f"window_connectivity: the {len(order)} x ({expect}, {nch}, "
+                              f"{nch}) float64 results need {need / 1e9:.2f} GB, more than the "
+                              f"{torch.cuda.mem_get_info()[0] / 1e9:.2f} GB of device memory that are free: "
+                              f"raise step (now {step}; winsize {W}) or select fewer of the {nch} channels")
+        out = torch.empty((len(order), n, nch, nch), dtype=torch.float64, device=x.device)
+        dev.window_pairs(x, W, step, ddof, mask, out)
+        parts.append(out.cpu().numpy() if host else out)
     planes = np.concatenate(parts, axis=1) if host else torch.cat(parts, dim=1)
     out = {name: planes[order.index(name)] for name in names}
-    return total, out[names[0]] if isinstance(measures, str) or not isinstance(measures, (tuple, list)) else out
+    return planes.shape[1], out[names[0]] if _stream._is_one(measures) else out

@@ -3,40 +3,18 @@ the reference) -- the pattern counts that ``window_features``, whose thirteen fe
 and extremes, leaves out.  Sample entropy is O(W^2) compare-and-count per window; the device kernel
 of ``csrc/windowent.hip`` (K16), ``osz_window_entropy``, holds the window in LDS and gives every
 measure asked from one read of the stream.  The windows, the streaming loop and the layout of the
-result are those of ``features/windowed.py``.
+result are those of ``window_features``: ``features/_stream.py``.
 """
 
 import math
 
-import numpy as np
-
 from openseize_amd import _device as dev
 from openseize_amd import _lib
-from openseize_amd.core.producer import Producer, producer
-from openseize_amd.features.windowed import (_PUSH_BYTES, _advance, _is_complex, window_count,  # noqa: F401
-                                             window_plan)
+from openseize_amd.features import _stream
+from openseize_amd.features._stream import _advance, window_count, window_plan  # noqa: F401  (the family's)
 
 WINDOW_ENTROPIES = tuple(_lib.WINDOW_ENTROPY)
 _SAMPLE = ("sample", "sample_a", "sample_b")
-
-
-def _names(measures):
-    names = (measures,) if isinstance(measures, str) or not isinstance(measures, (tuple, list)) else tuple(measures)
-    bad = [f for f in names if not isinstance(f, str) or f not in WINDOW_ENTROPIES]
-    if bad or not names:
-        raise ValueError(f"unknown window entropy measure(s) {bad}: choose from {WINDOW_ENTROPIES}")
-    return names
-
-
-def _size(value, least, most, what):
-    if (isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least
-            or (most is not None and value > most)):
-        span = f">= {least}" if most is None else f"from {least} to {most}"
-        raise ValueError(f"window_entropy: {what} must be an integer {span}, got {value!r}")
-    return int(value)
-
-
-_COMPLEX = "window_entropy takes real data, got {}"
 
 
 def window_entropy(data, winsize, step=None, measures=("sample", "permutation"), m=2, r=0.2, tolerance="std",
@@ -88,13 +66,14 @@ def window_entropy(data, winsize, step=None, measures=("sample", "permutation"),
     device is touched (a producer's complex chunks when the first one arrives); so does a stream
     shorter than ``winsize``.
     """
-    names = _names(measures)
-    W = _size(winsize, 4, _lib.WE_LONGEST, f"winsize (the longest window is {_lib.WE_LONGEST} samples)")
-    step = W if step is None else _size(step, 1, None, "step")
-    m = _size(m, 1, 8, "m")
-    order = _size(order, 2, 6, "order")
-    delay = _size(delay, 1, None, "delay")
-    if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)) or not math.isfinite(r) or r < 0:
+    who = "window_entropy"
+    names = _stream._names(measures, WINDOW_ENTROPIES, "window entropy measure(s)")
+    W = _stream._size(winsize, 4, _lib.WE_LONGEST, who, f"winsize (the longest window is {_lib.WE_LONGEST} samples)")
+    step = W if step is None else _stream._size(step, 1, None, who, "step")
+    m = _stream._size(m, 1, 8, who, "m")
+    order = _stream._size(order, 2, 6, who, "order")
+    delay = _stream._size(delay, 1, None, who, "delay")
+    if not _stream._is_real(r) or not math.isfinite(r) or r < 0:
         raise ValueError(f"window_entropy: r must be a finite float >= 0, got {r!r}")
     if not isinstance(tolerance, str) or tolerance not in _lib.WE_TOLERANCE:
         raise ValueError(f"window_entropy: unknown tolerance {tolerance!r}: choose from {tuple(_lib.WE_TOLERANCE)}")
@@ -103,56 +82,14 @@ def window_entropy(data, winsize, step=None, measures=("sample", "permutation"),
     if W <= (order - 1) * delay and "permutation" in names:
         raise ValueError(f"window_entropy: permutation entropy with order = {order}, delay = {delay} needs winsize > "
                          f"(order - 1) delay = {(order - 1) * delay}, got {W}")
-    if isinstance(data, Producer):
-        pro = producer(data, data.chunksize, axis)
-    else:
-        if dev.is_arraylike(data) and _is_complex(data):
-            raise ValueError(_COMPLEX.format(f"{data.dtype} data"))
-        pro = producer(data, int(10e6) if chunksize is None else chunksize, axis)
-    if not 1 <= len(pro.shape) <= 2:
-        raise ValueError(f"window_entropy needs one- or two-dimensional data, got shape {tuple(pro.shape)}: "
-                         "reshape the channel axes into one")
-    layout = dev.Layout(pro.shape, axis)
-    if pro.shape[layout.axis] < W:
-        raise ValueError(f"window_entropy: the stream holds {pro.shape[layout.axis]} samples, fewer than one "
-                         f"window of {W}")
+    kind = _stream._real_only(who)
+    pro, layout = _stream._open(who, data, axis, chunksize, W, kind)
     nch = layout.nch
-    planes = [f for f in WINDOW_ENTROPIES if f in names]     # the planes a push writes
-    mask = dev.entropy_mask(planes)
-    host = dev.origin_is_host(pro)
-    torch = dev.torch
-    most = max(1, _PUSH_BYTES // (8 * len(planes) * nch))    # windows per launch
-    parts, carry, skip, total, started = [], None, 0, 0, False
-    for arr in dev.pull_resident(pro, pro):
-        if _is_complex(arr):
-            raise ValueError(_COMPLEX.format(f"{arr.dtype} chunks"))
-        if not started:
-            dev.require_gpu()
-            started = True
-        x2d, was_host = layout.to2d(arr)
-        host = host or was_host
-        have = 0 if carry is None else carry.shape[1]
-        drop, nwin, keep, skip = _advance(have, skip, x2d.shape[1], W, step)
-        if drop:
-            x2d = x2d[:, drop:]
-        if carry is not None:
-            x2d = torch.cat((carry, x2d), dim=1)
-        for k0 in range(0, nwin, most):
-            k1 = min(k0 + most, nwin)
-            out = torch.empty((len(planes), nch, k1 - k0), dtype=torch.float64, device=x2d.device)
-            dev.window_entropy(x2d[:, k0 * step:(k1 - 1) * step + W], W, step, mask, m, r, tolerance, order, delay,
-                               normalize, out)
-            parts.append(out.cpu().numpy() if host else out)
-        total += nwin
-        # (a copy: a source may fill the chunk's memory again before the next push reads it)
-        carry = x2d[:, x2d.shape[1] - keep:].clone() if keep else None
-    if total == 0:
-        raise ValueError(f"window_entropy: the stream ended before one window of {W} samples was full")
-    if host:
-        stacked = np.concatenate(parts, axis=2)
-        shaped = [np.moveaxis(p.reshape(layout.other + (total,)), -1, layout.axis) for p in stacked]
-    else:
-        stacked = torch.cat(parts, dim=2)
-        shaped = [layout.from2d(p, False) for p in stacked]
-    out = {name: shaped[planes.index(name)] for name in names}
-    return total, out[names[0]] if isinstance(measures, str) or not isinstance(measures, (tuple, list)) else out
+    planes = [f for f in WINDOW_ENTROPIES if f in names]     # the planes a launch writes
+    mask = dev.name_mask(_lib.WINDOW_ENTROPY, planes)
+    parts, host = [], None
+    for x, n, host in _stream._launches(who, pro, W, step, kind, layout.to2d, 8 * len(planes) * nch):
+        out = dev.torch.empty((len(planes), nch, n), dtype=dev.torch.float64, device=x.device)
+        dev.window_entropy(x, W, step, mask, m, r, tolerance, order, delay, normalize, out)
+        parts.append(out.cpu().numpy() if host else out)
+    return _stream._result(parts, host, layout, measures, names, {f: (i, None) for i, f in enumerate(planes)})

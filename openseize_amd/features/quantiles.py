@@ -4,7 +4,7 @@ extremes) and ``window_entropy`` (pattern counts) leave out: a robust baseline a
 quantile envelope, the interquartile range.  The device kernel of ``csrc/windowquant.hip`` (K17),
 ``osz_window_quantiles``, sorts each window on chip from one read of the stream and gives every
 measure asked.  The windows, the streaming loop and the layout of the result are those of
-``features/windowed.py``.
+``window_features``: ``features/_stream.py``.
 """
 
 import math
@@ -13,31 +13,11 @@ import numpy as np
 
 from openseize_amd import _device as dev
 from openseize_amd import _lib
-from openseize_amd.core.producer import Producer, producer
-from openseize_amd.features.windowed import (_PUSH_BYTES, _advance, _is_complex, window_count,  # noqa: F401
-                                             window_plan)
+from openseize_amd.features import _stream
+from openseize_amd.features._stream import _advance, window_count, window_plan  # noqa: F401  (the family's)
+from openseize_amd.features._stream import _is_real
 
 WINDOW_QUANTILES = tuple(_lib.WINDOW_QUANTILE)
-
-
-def _names(measures):
-    names = (measures,) if isinstance(measures, str) or not isinstance(measures, (tuple, list)) else tuple(measures)
-    bad = [f for f in names if not isinstance(f, str) or f not in WINDOW_QUANTILES]
-    if bad or not names:
-        raise ValueError(f"unknown window quantile measure(s) {bad}: choose from {WINDOW_QUANTILES}")
-    return names
-
-
-def _size(value, least, most, what):
-    if (isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least
-            or (most is not None and value > most)):
-        span = f">= {least}" if most is None else f"from {least} to {most}"
-        raise ValueError(f"window_quantiles: {what} must be an integer {span}, got {value!r}")
-    return int(value)
-
-
-def _is_real(p):
-    return not isinstance(p, bool) and isinstance(p, (int, float, np.integer, np.floating))
 
 
 def _probabilities(q):
@@ -52,9 +32,6 @@ def _probabilities(q):
         if not _is_real(p) or not math.isfinite(p) or not 0.0 <= p <= 1.0:
             raise ValueError(f"window_quantiles: every q must be a finite float in [0, 1], got {p!r}")
     return [float(p) for p in values], scalar
-
-
-_COMPLEX = "window_quantiles takes real data, got {}"
 
 
 def window_quantiles(data, winsize, step=None, measures=("median", "mad"), q=(0.25, 0.75), axis=-1, chunksize=None):
@@ -104,66 +81,23 @@ def window_quantiles(data, winsize, step=None, measures=("median", "mad"), q=(0.
     stream or the device is touched (a producer's complex chunks when the first one arrives); so
     does a stream shorter than ``winsize``.
     """
-    names = _names(measures)
-    W = _size(winsize, 4, _lib.WQ_LONGEST, f"winsize (the longest window is {_lib.WQ_LONGEST} samples)")
-    step = W if step is None else _size(step, 1, None, "step")
+    who = "window_quantiles"
+    names = _stream._names(measures, WINDOW_QUANTILES, "window quantile measure(s)")
+    W = _stream._size(winsize, 4, _lib.WQ_LONGEST, who, f"winsize (the longest window is {_lib.WQ_LONGEST} samples)")
+    step = W if step is None else _stream._size(step, 1, None, who, "step")
     qs, scalar = _probabilities(q) if "quantile" in names else ([], True)
-    if isinstance(data, Producer):
-        pro = producer(data, data.chunksize, axis)
-    else:
-        if dev.is_arraylike(data) and _is_complex(data):
-            raise ValueError(_COMPLEX.format(f"{data.dtype} data"))
-        pro = producer(data, int(10e6) if chunksize is None else chunksize, axis)
-    if not 1 <= len(pro.shape) <= 2:
-        raise ValueError(f"window_quantiles needs one- or two-dimensional data, got shape {tuple(pro.shape)}: "
-                         "reshape the channel axes into one")
-    layout = dev.Layout(pro.shape, axis)
-    if pro.shape[layout.axis] < W:
-        raise ValueError(f"window_quantiles: the stream holds {pro.shape[layout.axis]} samples, fewer than one "
-                         f"window of {W}")
+    kind = _stream._real_only(who)
+    pro, layout = _stream._open(who, data, axis, chunksize, W, kind)
     nch = layout.nch
-    present = [f for f in WINDOW_QUANTILES if f in names]    # the measures a push writes, in the kernel's order
-    mask = dev.quantile_mask(present)
-    first = {f: sum(len(qs) if g == "quantile" else 1 for g in present[:i]) for i, f in enumerate(present)}
-    nplanes = first[present[-1]] + (len(qs) if present[-1] == "quantile" else 1)
-    host = dev.origin_is_host(pro)
-    torch = dev.torch
-    most = max(1, _PUSH_BYTES // (8 * nplanes * nch))        # windows per launch
-    parts, carry, skip, total, started = [], None, 0, 0, False
-    for arr in dev.pull_resident(pro, pro):
-        if _is_complex(arr):
-            raise ValueError(_COMPLEX.format(f"{arr.dtype} chunks"))
-        if not started:
-            dev.require_gpu()
-            started = True
-        x2d, was_host = layout.to2d(arr)
-        host = host or was_host
-        have = 0 if carry is None else carry.shape[1]
-        drop, nwin, keep, skip = _advance(have, skip, x2d.shape[1], W, step)
-        if drop:
-            x2d = x2d[:, drop:]
-        if carry is not None:
-            x2d = torch.cat((carry, x2d), dim=1)
-        for k0 in range(0, nwin, most):
-            k1 = min(k0 + most, nwin)
-            out = torch.empty((nplanes, nch, k1 - k0), dtype=torch.float64, device=x2d.device)
-            dev.window_quantiles(x2d[:, k0 * step:(k1 - 1) * step + W], W, step, mask, qs, out)
-            parts.append(out.cpu().numpy() if host else out)
-        total += nwin
-        # (a copy: a source may fill the chunk's memory again before the next push reads it)
-        carry = x2d[:, x2d.shape[1] - keep:].clone() if keep else None
-    if total == 0:
-        raise ValueError(f"window_quantiles: the stream ended before one window of {W} samples was full")
-    if host:
-        stacked = np.concatenate(parts, axis=2)
-        shaped = [np.moveaxis(p.reshape(layout.other + (total,)), -1, layout.axis) for p in stacked]
-        stack = np.stack
-    else:
-        stacked = torch.cat(parts, dim=2)
-        shaped = [layout.from2d(p, False) for p in stacked]
-        stack = torch.stack
-    out = {}
-    for name in names:
-        p = first[name]
-        out[name] = shaped[p] if name != "quantile" or scalar else stack(shaped[p:p + len(qs)])
-    return total, out[names[0]] if isinstance(measures, str) or not isinstance(measures, (tuple, list)) else out
+    present = [f for f in WINDOW_QUANTILES if f in names]    # the measures a launch writes, in the kernel's order
+    mask = dev.name_mask(_lib.WINDOW_QUANTILE, present)
+    width = {f: len(qs) if f == "quantile" else 1 for f in present}
+    where = {f: (sum(width[g] for g in present[:i]), None if f != "quantile" or scalar else len(qs))
+             for i, f in enumerate(present)}
+    nplanes = sum(width.values())
+    parts, host = [], None
+    for x, n, host in _stream._launches(who, pro, W, step, kind, layout.to2d, 8 * nplanes * nch):
+        out = dev.torch.empty((nplanes, nch, n), dtype=dev.torch.float64, device=x.device)
+        dev.window_quantiles(x, W, step, mask, qs, out)
+        parts.append(out.cpu().numpy() if host else out)
+    return _stream._result(parts, host, layout, measures, names, where)

@@ -6,7 +6,7 @@ seizure detection and depth-of-anaesthesia features are built from, and what ``w
 leave out.  The periodograms are those of ``stft``: the segmenter and transforms of ``csrc/spec.hip``;
 the device kernel of ``csrc/windowspec.hip`` (K18), ``osz_spectral_features``, reduces each of them
 in one launch per push, so the (C, nfreq, nseg) spectrogram is never held.  The windows and the
-layout of the result are those of ``features/windowed.py``.
+layout of the result are those of ``window_features``: ``features/_stream.py``.
 """
 
 import math
@@ -16,8 +16,8 @@ import numpy as np
 from openseize_amd import _device as dev
 from openseize_amd import _lib
 from openseize_amd.core import numerical as nm
-from openseize_amd.core.producer import Producer, producer
-from openseize_amd.features.windowed import _is_complex
+from openseize_amd.features import _stream
+from openseize_amd.features._stream import _is_complex, _is_real
 
 WINDOW_SPECTRAL = tuple(_lib.WINDOW_SPECTRAL)
 
@@ -25,26 +25,6 @@ WINDOW_SPECTRAL = tuple(_lib.WINDOW_SPECTRAL)
 # benchmarks/spectral_probe.py: bounds of 64, 128 and 256 MiB, which would keep a push's periodograms
 # in the Infinity Cache, measured 2 .. 30 % slower than this one -- more launches, nothing gained.
 _SPECTRAL_PUSH_BYTES = 1 << 30
-
-
-def _names(features):
-    names = (features,) if isinstance(features, str) or not isinstance(features, (tuple, list)) else tuple(features)
-    bad = [f for f in names if not isinstance(f, str) or f not in WINDOW_SPECTRAL]
-    if bad or not names:
-        raise ValueError(f"unknown window spectral feature(s) {bad}: choose from {WINDOW_SPECTRAL}")
-    return names
-
-
-def _size(value, least, most, what):
-    if (isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least
-            or (most is not None and value > most)):
-        span = f">= {least}" if most is None else f"from {least} to {most}"
-        raise ValueError(f"window_spectral: {what} must be an integer {span}, got {value!r}")
-    return int(value)
-
-
-def _is_real(p):
-    return not isinstance(p, bool) and isinstance(p, (int, float, np.integer, np.floating))
 
 
 def _frequency(value, what):
@@ -109,9 +89,6 @@ def _fractions(edge):
         if not _is_real(p) or not math.isfinite(p) or not 0.0 < p <= 1.0:
             raise ValueError(f"window_spectral: every edge must be a finite float in (0, 1], got {p!r}")
     return [float(p) for p in values], scalar
-
-
-_COMPLEX = "window_spectral takes real data, got {}"
 
 
 def window_spectral(data, fs, winsize, step=None, features=("total", "edge", "entropy"), bands=None, edge=0.95,
@@ -179,12 +156,13 @@ def window_spectral(data, fs, winsize, step=None, features=("total", "edge", "en
     touched (a producer's complex chunks when the first one arrives); so does a stream shorter
     than ``winsize``.
     """
-    names = _names(features)
-    W = _size(winsize, 8, None, "winsize")
+    who = "window_spectral"
+    names = _stream._names(features, WINDOW_SPECTRAL, "window spectral feature(s)")
+    W = _stream._size(winsize, 8, None, who, "winsize")
     if step is not None and not isinstance(step, bool) and isinstance(step, (int, np.integer)) and step > W:
         raise ValueError(f"window_spectral: step = {step} is larger than winsize = {W}: the segmenter has no gaps, "
                          "step must be from 1 to winsize")
-    step = W if step is None else _size(step, 1, W, "step")
+    step = W if step is None else _stream._size(step, 1, W, who, "step")
     fs = _frequency(fs, "fs")
     if fs <= 0:
         raise ValueError(f"window_spectral: fs must be positive, got {fs!r}")
@@ -199,35 +177,25 @@ def window_spectral(data, fs, winsize, step=None, features=("total", "edge", "en
         raise ValueError("window_spectral: 'band' and 'relative' need bands, a (lo, hi) pair or a sequence of pairs")
     bins, one_band = _band_bins(bands, freqs, k0, k1) if banded else ([], True)
     fracs, one_edge = _fractions(edge) if "edge" in names else ([], True)
-    if isinstance(data, Producer):
-        pro = producer(data, data.chunksize, axis)
-    else:
-        if dev.is_arraylike(data) and _is_complex(data):
-            raise ValueError(_COMPLEX.format(f"{data.dtype} data"))
-        pro = producer(data, int(10e6) if chunksize is None else chunksize, axis)
-    if not 1 <= len(pro.shape) <= 2:
-        raise ValueError(f"window_spectral needs one- or two-dimensional data, got shape {tuple(pro.shape)}: "
-                         "reshape the channel axes into one")
-    layout = dev.Layout(pro.shape, axis)
-    if pro.shape[layout.axis] < W:
-        raise ValueError(f"window_spectral: the stream holds {pro.shape[layout.axis]} samples, fewer than one "
-                         f"window of {W}")
+    kind = _stream._real_only(who)
+    pro, layout = _stream._open(who, data, axis, chunksize, W, kind)
     coeffs, scale = nm._window_and_scale(window, W, fs, scaling)
     nch, nfreq = layout.nch, W // 2 + 1
     df = float(fs) / W
     present = [f for f in WINDOW_SPECTRAL if f in names]     # the features a push writes, in the kernel's order
     mask = dev.spectral_mask(present)
     width = {f: len(bins) if f in ("band", "relative") else len(fracs) if f == "edge" else 1 for f in present}
-    first = {f: sum(width[g] for g in present[:i]) for i, f in enumerate(present)}
+    single = {"band": one_band, "relative": one_band, "edge": one_edge}
+    where = {f: (sum(width[g] for g in present[:i]), None if single.get(f, True) else width[f])
+             for i, f in enumerate(present)}
     nplanes = dev.spectral_planes(mask, len(bins), len(fracs))
     host = dev.origin_is_host(pro)
     torch = dev.torch
     cap = max(1, _SPECTRAL_PUSH_BYTES // (8 * nch * nfreq)) * step       # samples per push
-    parts, total, spec = [], 0, None
+    parts, spec = [], None
     try:
         for arr in dev.pull_resident(pro, pro):
-            if _is_complex(arr):
-                raise ValueError(_COMPLEX.format(f"{arr.dtype} chunks"))
+            kind(_is_complex(arr), f"{arr.dtype} chunks")
             if spec is None:
                 dev.require_gpu()
                 spec = dev.SpecStream(W, W, step, coeffs, scale, detrend, _lib.SPEC_PSD_SEGMENTS, nch)
@@ -244,23 +212,9 @@ def window_spectral(data, fs, winsize, step=None, features=("total", "edge", "en
                 out = torch.empty((nplanes, nch, nseg), dtype=torch.float64, device=P.device)
                 dev.spectral_features(P, k0, k1, df, bins, fracs, normalize, mask, out)
                 parts.append(out.cpu().numpy() if host else out)
-                total += nseg
     finally:
         if spec is not None:
             spec.close()
-    if total == 0:
+    if not parts:
         raise ValueError(f"window_spectral: the stream ended before one window of {W} samples was full")
-    if host:
-        stacked = np.concatenate(parts, axis=2)
-        shaped = [np.moveaxis(p.reshape(layout.other + (total,)), -1, layout.axis) for p in stacked]
-        stack = np.stack
-    else:
-        stacked = torch.cat(parts, dim=2)
-        shaped = [layout.from2d(p, False) for p in stacked]
-        stack = torch.stack
-    single = {"band": one_band, "relative": one_band, "edge": one_edge}
-    out = {}
-    for name in names:
-        p = first[name]
-        out[name] = shaped[p] if single.get(name, True) else stack(shaped[p:p + width[name]])
-    return total, out[names[0]] if isinstance(features, str) or not isinstance(features, (tuple, list)) else out
+    return _stream._result(parts, host, layout, features, names, where)

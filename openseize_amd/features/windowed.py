@@ -6,72 +6,12 @@ from one read of the data by the device kernel of ``csrc/windowfeat.hip`` (K15):
 ``osz_window_features``.
 """
 
-import numpy as np
-
 from openseize_amd import _device as dev
 from openseize_amd import _lib
-from openseize_amd.core.producer import Producer, producer
+from openseize_amd.features import _stream
+from openseize_amd.features._stream import _advance, window_count, window_plan  # noqa: F401  (the family's)
 
 WINDOW_FEATURES = tuple(_lib.WINDOW_FEATURE)
-
-# bytes of results one push may write (the samples of a push are the source's chunk and the carry)
-_PUSH_BYTES = 1 << 30
-
-
-def _names(features):
-    names = (features,) if isinstance(features, str) or not isinstance(features, (tuple, list)) else tuple(features)
-    bad = [f for f in names if not isinstance(f, str) or f not in WINDOW_FEATURES]
-    if bad or not names:
-        raise ValueError(f"unknown window feature(s) {bad}: choose from {WINDOW_FEATURES}")
-    return names
-
-
-def _size(value, least, what):
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least:
-        raise ValueError(f"window_features: {what} must be an integer >= {least}, got {value!r}")
-    return int(value)
-
-
-def window_count(n, winsize, step):
-    """The windows of ``winsize`` samples, ``step`` apart, that ``n`` samples hold (a trailing
-    window the samples do not fill is dropped)."""
-    return 0 if n < winsize else (n - winsize) // step + 1
-
-
-def _advance(have, skip, m, winsize, step):
-    """One chunk of ``m`` samples arrives with ``have`` samples carried (they start at the next
-    unfinished window) and ``skip`` samples still to discard in front of that window (a gap,
-    ``step > winsize``, that the last chunk ended in).  Returns ``(drop, nwin, keep, skip)``:
-    ``drop`` samples leave the chunk's front, the carry and the rest hold ``nwin`` whole windows,
-    their last ``keep`` samples are carried on, and ``skip`` are still to discard."""
-    drop = min(skip, m)
-    avail = have + m - drop
-    nwin = window_count(avail, winsize, step)
-    used = nwin * step                          # where the next unfinished window starts
-    if used <= avail:
-        return drop, nwin, avail - used, skip - drop
-    return drop, nwin, 0, skip - drop + used - avail
-
-
-def window_plan(lengths, winsize, step):
-    """The bookkeeping of the streaming loop as a function of the chunk lengths alone: per chunk
-    ``(start, nwin, keep, skip)`` -- the stream index of the first sample the push holds (carry
-    included), the windows it completes, the samples carried on and the samples of a gap still to
-    discard."""
-    plan, have, skip, seen = [], 0, 0, 0
-    for m in lengths:
-        drop, nwin, keep, skip = _advance(have, skip, m, winsize, step)
-        plan.append((seen + drop - have, nwin, keep, skip))
-        seen += m
-        have = keep
-    return plan
-
-
-_COMPLEX = "window_features takes real data, got {}"
-
-
-def _is_complex(arr):
-    return arr.is_complex() if dev.is_tensor(arr) else np.iscomplexobj(arr)
 
 
 def window_features(data, winsize, step=None, features=("line_length", "var"), axis=-1, chunksize=None):
@@ -118,58 +58,18 @@ def window_features(data, winsize, step=None, features=("line_length", "var"), a
     samples (or, between two chunks, the unfinished windows' samples) are carried, and each push's
     results come down as they are made; CUDA-fed streams keep theirs on the device.
     """
-    names = _names(features)
-    W = _size(winsize, 4, "winsize")
-    step = W if step is None else _size(step, 1, "step")
-    if isinstance(data, Producer):
-        pro = producer(data, data.chunksize, axis)
-    else:
-        if dev.is_arraylike(data) and _is_complex(data):
-            raise ValueError(_COMPLEX.format(f"{data.dtype} data"))
-        pro = producer(data, int(10e6) if chunksize is None else chunksize, axis)
-    if not 1 <= len(pro.shape) <= 2:
-        raise ValueError(f"window_features needs one- or two-dimensional data, got shape {tuple(pro.shape)}: "
-                         "reshape the channel axes into one")
-    layout = dev.Layout(pro.shape, axis)
-    if pro.shape[layout.axis] < W:
-        raise ValueError(f"window_features: the stream holds {pro.shape[layout.axis]} samples, fewer than one "
-                         f"window of {W}")
+    who = "window_features"
+    names = _stream._names(features, WINDOW_FEATURES, "window feature(s)")
+    W = _stream._size(winsize, 4, None, who, "winsize")
+    step = W if step is None else _stream._size(step, 1, None, who, "step")
+    kind = _stream._real_only(who)
+    pro, layout = _stream._open(who, data, axis, chunksize, W, kind)
     nch = layout.nch
-    order = [f for f in WINDOW_FEATURES if f in names]       # the planes a push writes
-    mask = dev.window_mask(order)
-    host = dev.origin_is_host(pro)
-    torch = dev.torch
-    most = max(1, _PUSH_BYTES // (8 * len(order) * nch))     # windows per launch
-    parts, carry, skip, total, started = [], None, 0, 0, False
-    for arr in dev.pull_resident(pro, pro):
-        if _is_complex(arr):
-            raise ValueError(_COMPLEX.format(f"{arr.dtype} chunks"))
-        if not started:
-            dev.require_gpu()
-            started = True
-        x2d, was_host = layout.to2d(arr)
-        host = host or was_host
-        have = 0 if carry is None else carry.shape[1]
-        drop, nwin, keep, skip = _advance(have, skip, x2d.shape[1], W, step)
-        if drop:
-            x2d = x2d[:, drop:]
-        if carry is not None:
-            x2d = torch.cat((carry, x2d), dim=1)
-        for k0 in range(0, nwin, most):
-            k1 = min(k0 + most, nwin)
-            out = torch.empty((len(order), nch, k1 - k0), dtype=torch.float64, device=x2d.device)
-            dev.window_features(x2d[:, k0 * step:(k1 - 1) * step + W], W, step, mask, out)
-            parts.append(out.cpu().numpy() if host else out)
-        total += nwin
-        # (a copy: a source may fill the chunk's memory again before the next push reads it)
-        carry = x2d[:, x2d.shape[1] - keep:].clone() if keep else None
-    if total == 0:
-        raise ValueError(f"window_features: the stream ended before one window of {W} samples was full")
-    if host:
-        planes = np.concatenate(parts, axis=2)
-        shaped = [np.moveaxis(p.reshape(layout.other + (total,)), -1, layout.axis) for p in planes]
-    else:
-        planes = torch.cat(parts, dim=2)
-        shaped = [layout.from2d(p, False) for p in planes]
-    out = {name: shaped[order.index(name)] for name in names}
-    return total, out[names[0]] if isinstance(features, str) or not isinstance(features, (tuple, list)) else out
+    order = [f for f in WINDOW_FEATURES if f in names]       # the planes a launch writes
+    mask = dev.name_mask(_lib.WINDOW_FEATURE, order)
+    parts, host = [], None
+    for x, n, host in _stream._launches(who, pro, W, step, kind, layout.to2d, 8 * len(order) * nch):
+        out = dev.torch.empty((len(order), nch, n), dtype=dev.torch.float64, device=x.device)
+        dev.window_features(x, W, step, mask, out)
+        parts.append(out.cpu().numpy() if host else out)
+    return _stream._result(parts, host, layout, features, names, {f: (i, None) for i, f in enumerate(order)})
