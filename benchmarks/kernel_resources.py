@@ -2,6 +2,11 @@
 reports it for gfx950 (-Rpass-analysis=kernel-resource-usage):
 
     python benchmarks/kernel_resources.py openseize_amd/csrc/chain_spec.hip [filter]
+
+With `-` for the source the remarks are read from standard input -- the log of a build of the
+library with the same flag (make -O CXXFLAGS="... -Rpass-analysis=kernel-resource-usage"):
+
+    python benchmarks/kernel_resources.py - chain_zpn_kernel < build.log
 """
 import re
 import subprocess
@@ -11,9 +16,12 @@ import sys
 def main():
     src = sys.argv[1]
     flt = sys.argv[2] if len(sys.argv) > 2 else ""
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-c", src,
-           "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[3:]
-    out = subprocess.run(cmd, capture_output=True, text=True).stderr
+    if src == "-":
+        out = sys.stdin.read()
+    else:
+        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-c", src,
+               "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[3:]
+        out = subprocess.run(cmd, capture_output=True, text=True).stderr
     rows, cur = [], None
     for line in out.splitlines():
         m = re.search(r"remark: +([A-Za-z ]+?)(?: \[bytes/lane\]| \[waves/SIMD\]| \[bytes/block\])?: (\S+)", line)

@@ -166,18 +166,24 @@ __device__ __forceinline__ void zpn_fwd_bursts(double *re, const double *kmu, co
 // The backward bursts (RB rows): this block's nu leaves window row 31 - r (im[15 - r]) and
 // arrives, with the same values, in the rows the previous block holds back (c7).  The slow modes
 // in every row; the fast ones (all at once: one more round of table reads, not one per pair)
-// in the first.
-template <int NM, int NS, int RB>
+// in the first.  RES: the fast modes' powers come in Fr / Fi (the resident instances); otherwise
+// they are formed here, from ptab at exponent e.
+template <int NM, int NS, int RB, bool RES>
 __device__ __forceinline__ void zpn_bwd_bursts(double *im, double *c7, const double *knu, const double *ptab, int e,
-                                               const double *Pr, const double *Pi) {
+                                               const double *Pr, const double *Pi, const double *Fr,
+                                               const double *Fi) {
     double nb[RB];
 #pragma unroll
     for (int r = 0; r < RB; ++r) nb[r] = zp_dot<NS>(knu + (r * NM) * 2, Pr, Pi);
     if (NM > NS) {
         constexpr int NF = NM > NS ? NM - NS : 1;
-        double fr[NF], fi[NF];
-        zpn_powers<NM, NF>(ptab, NS, e, fr, fi);
-        nb[0] += zp_dot<NF>(knu + NS * 2, fr, fi);
+        if (RES) {
+            nb[0] += zp_dot<NF>(knu + NS * 2, Fr, Fi);
+        } else {
+            double fr[NF], fi[NF];
+            zpn_powers<NM, NF>(ptab, NS, e, fr, fi);
+            nb[0] += zp_dot<NF>(knu + NS * 2, fr, fi);
+        }
     }
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
@@ -185,6 +191,19 @@ __device__ __forceinline__ void zpn_bwd_bursts(double *im, double *c7, const dou
         c7[r] = nb[r];
     }
 }
+
+// Which instances keep their mode powers in registers for the whole launch.  The powers of a
+// thread -- lambda_q^t of the slow modes for the forward bursts, lambda_q^(255 - t) of every mode
+// for the backward ones -- are the same in every block; formed per block each of the NS + NM
+// powers costs two complex products and three table reads behind the fit's barrier.  Resident
+// they take 2 (NS + NM) register pairs, which the allocator has only where the transform loads the spectrum in two
+// halves (NegaWindow::transform<NP, SPLIT>) and the instance is one of the lean ones.  Settled
+// per instance from the compiler's report (profiles/zpn_resident_resources.txt: no spill, no more
+// scratch than without, two workgroups per CU), not a global switch: two slow modes and five
+// burst rows; of the zero-phase instances those of up to four modes, and of six modes from 27
+// rows on (the lower blocks carry more tail rows across, eight modes two more fast powers).
+template <int NB, int NM, int NS, int RM, bool ZP>
+constexpr bool zpn_resident = RM == kSpecRMax && NS == 2 && (!ZP || NM <= 4 || (NM == 6 && NB >= 27));
 
 // RM: burst rows the instance holds registers for (5, or 8 for the long left tails of blocks of
 // 24 ... 26 rows).  ZP = false: the FORWARD chain (FIR -> sosfilt, chain_spec.hip's
@@ -257,6 +276,16 @@ __global__ __launch_bounds__(256, 2) void chain_zpn_kernel(ZpArgs g) {
     int par = 0;
     int younger = -1;                // vector-memory operations behind the pending requests
     __syncthreads();
+    // the resident instances' mode powers, once per launch (the tables are in LDS now): lambda^t of
+    // the slow modes, lambda^(255 - t) of the slow and of the fast ones
+    constexpr bool RES = zpn_resident<NB, NM, NS, RM, ZP>;
+    constexpr int NF = NM > NS ? NM - NS : 1;
+    double rPr[NS], rPi[NS], rQr[NS], rQi[NS], rFr[NF], rFi[NF];
+    if (RES) {
+        zpn_powers<NM, NS>(ptab, 0, t, rPr, rPi);
+        if (ZP) zpn_powers<NM, NS>(ptab, 0, 255 - t, rQr, rQi);
+        if (ZP && NM > NS) zpn_powers<NM, NF>(ptab, NS, 255 - t, rFr, rFi);
+    }
 
     // a sample of the chunk (position i, value v) goes to the output, L samples late, or,
     // the chunk's last L samples, to `held`
@@ -300,7 +329,7 @@ __global__ __launch_bounds__(256, 2) void chain_zpn_kernel(ZpArgs g) {
         }
         // (the next block's samples are requested inside, once inverse pass 1 has read this wave's
         // pieces of the cube: they land while its arithmetic, fit, bursts and stores run)
-        P.template transform<NP>(t, re, im, (!closing && p < lastf) ? xr + o + S : nullptr, NB);
+        P.template transform<NP, RES>(t, re, im, (!closing && p < lastf) ? xr + o + S : nullptr, NB);
         int nst = 0;             // row stores of this block, -1: some went another way
         int tt = t;
         asm volatile("" : "+v"(tt));
@@ -318,8 +347,9 @@ __global__ __launch_bounds__(256, 2) void chain_zpn_kernel(ZpArgs g) {
 #pragma unroll
         for (int r = 0; r < RM; ++r) c7[r] = 0.0;
         {
-            double Pr[NS], Pi[NS];
-            zpn_powers<NM, NS>(ptab, 0, tt, Pr, Pi);
+            double bPr[NS], bPi[NS];
+            if (!RES) zpn_powers<NM, NS>(ptab, 0, tt, bPr, bPi);
+            const double *Pr = RES ? rPr : bPr, *Pi = RES ? rPi : bPi;
             const double *kpm = kapP + par * (Rt * NS * 2);
             double ca = 0.0;
             switch (Rf) {
@@ -331,21 +361,22 @@ __global__ __launch_bounds__(256, 2) void chain_zpn_kernel(ZpArgs g) {
             }
             // (no fence between the two halves: with two slow modes both sets of powers fit beside
             // the data, and the backward half's table reads go out behind the forward half's)
-            double Qr[NS], Qi[NS];
-            if (ZP) zpn_powers<NM, NS>(ptab, 0, 255 - tt, Qr, Qi);
+            double bQr[NS], bQi[NS];
+            if (ZP && !RES) zpn_powers<NM, NS>(ptab, 0, 255 - tt, bQr, bQi);
+            const double *Qr = RES ? rQr : bQr, *Qi = RES ? rQi : bQi;
             if (ZP) switch (R) {
-                case 1: zpn_bwd_bursts<NM, NS, 1>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
-                case 2: zpn_bwd_bursts<NM, NS, 2>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
-                case 3: zpn_bwd_bursts<NM, NS, 3>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
-                case 4: zpn_bwd_bursts<NM, NS, 4>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
-                case 5: zpn_bwd_bursts<NM, NS, 5>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
-                case 6: zpn_bwd_bursts<NM, NS, RM >= 6 ? 6 : 5>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
-                case 7: zpn_bwd_bursts<NM, NS, RM >= 7 ? 7 : 5>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
-                case 8: zpn_bwd_bursts<NM, NS, RM >= 8 ? 8 : 5>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
-                case 9: zpn_bwd_bursts<NM, NS, RM >= 9 ? 9 : 5>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
-                case 10: zpn_bwd_bursts<NM, NS, RM >= 10 ? 10 : 5>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
-                case 11: zpn_bwd_bursts<NM, NS, RM >= 11 ? 11 : 5>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
-                default: zpn_bwd_bursts<NM, NS, RM >= 12 ? 12 : 5>(im, c7, knu, ptab, 255 - tt, Qr, Qi); break;
+                case 1: zpn_bwd_bursts<NM, NS, 1, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
+                case 2: zpn_bwd_bursts<NM, NS, 2, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
+                case 3: zpn_bwd_bursts<NM, NS, 3, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
+                case 4: zpn_bwd_bursts<NM, NS, 4, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
+                case 5: zpn_bwd_bursts<NM, NS, 5, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
+                case 6: zpn_bwd_bursts<NM, NS, RM >= 6 ? 6 : 5, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
+                case 7: zpn_bwd_bursts<NM, NS, RM >= 7 ? 7 : 5, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
+                case 8: zpn_bwd_bursts<NM, NS, RM >= 8 ? 8 : 5, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
+                case 9: zpn_bwd_bursts<NM, NS, RM >= 9 ? 9 : 5, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
+                case 10: zpn_bwd_bursts<NM, NS, RM >= 10 ? 10 : 5, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
+                case 11: zpn_bwd_bursts<NM, NS, RM >= 11 ? 11 : 5, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
+                default: zpn_bwd_bursts<NM, NS, RM >= 12 ? 12 : 5, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
             }
             // non-finite samples are everywhere behind the transform: every amplitude of the fit
             // and with it every lane's burst values (looked at once, behind both halves)
@@ -416,8 +447,9 @@ __global__ __launch_bounds__(256, 2) void chain_zpn_kernel(ZpArgs g) {
                 else if (!bad && pp - la < kSpecLdc) co[pp - la] = v;
             }
             if (!bad) {
-                double Pr[NS], Pi[NS];
-                zpn_powers<NM, NS>(ptab, 0, tt, Pr, Pi);
+                double bPr[NS], bPi[NS];
+                if (!RES) zpn_powers<NM, NS>(ptab, 0, tt, bPr, bPi);
+                const double *Pr = RES ? rPr : bPr, *Pi = RES ? rPi : bPi;
                 for (int r = 0; r < Rf; ++r) {
                     const int k = 8192 + 256 * r + tt - la;
                     if (k < kSpecLdc) co[k] = zp_dot<NS>(kmu + (r * NS) * 2, Pr, Pi);

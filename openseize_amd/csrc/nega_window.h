@@ -66,8 +66,12 @@ struct NegaWindow {
 
     // next: where the NEXT block's rows begin (nrows of them), or null -- requested by LDS-DMA as
     // soon as inverse pass 1 has read this wave's pieces of the cube, ahead of its arithmetic:
-    // they land while that, the caller's epilogue and its stores run
-    template <int NP = 1>
+    // they land while that, the caller's epilogue and its stores run.
+    // SPLIT: the spectrum's bins 8 .. 15 are requested behind the fence, not in front of it -- only
+    // eight of the sixteen sit beside pass 2's data, which leaves the caller 32 registers to keep
+    // across blocks (chain_zpn_body.h: the resident mode powers); the second half has pass 3's LDS
+    // reads and butterfly to arrive behind
+    template <int NP = 1, bool SPLIT = false>
     __device__ __forceinline__ void transform(int t_in, double *re, double *im, const double *next = nullptr,
                                               int nrows = 0) {
         // LDS slot numbers are recomputed per block from an opaque copy of the thread index:
@@ -85,12 +89,20 @@ struct NegaWindow {
         const unsigned lane16 = 16u * ((unsigned)t & 255u);
         const __amdgpu_buffer_rsrc_t rh = buf_rsrc(a.H);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
+        for (int r = 0; r < (SPLIT ? 8 : 16); ++r) {
             const buf_d2 h = buf_load2(rh, lane16, 4096u * r);
             hr[r] = h.x;
             hi[r] = h.y;
         }
         wave_lds_fence();
+        if (SPLIT) {
+#pragma unroll
+            for (int r = 8; r < 16; ++r) {
+                const buf_d2 h = buf_load2(rh, lane16, 4096u * r);
+                hr[r] = h.x;
+                hi[r] = h.y;
+            }
+        }
         fft::cube2::f3(t, re, im, L);
 #pragma unroll
         for (int r = 0; r < 16; ++r) fft::cube::cmul(re[r], im[r], hr[r], hi[r]);
