@@ -2,86 +2,68 @@
 // acc[i, j, f] += sum_s conj(X[s, i, f]) X[s, j, f] (i <= j) of the segment spectra a
 // SPEC_DFT_SEGMENTS push wrote, and the finishing pass (mean, one-sided doubling, Hermitian
 // mirror, or the magnitude-squared coherence).  DESIGN.md section 3, K10.
-#include "common.h"
+#include "pair_tile.h"
 
 namespace osz {
 
-typedef double cx __attribute__((ext_vector_type(2)));   // (re, im) of one complex128
+// 4 x 4 waves: a 16 x 16 block of pairs; wave w stages row w of either set
+using CrossTile = PairTile<4, 1, true>;
 
-constexpr int kCrossT = 4;                    // channels per side of a lane's register tile
-constexpr int kCrossW = 4;                    // waves per side of a workgroup's tile
-constexpr int kCrossB = kCrossT * kCrossW;    // channels per side of a workgroup's tile (16)
-constexpr int kCrossThreads = kWave * kCrossW * kCrossW;   // 1024
-
-// A lane is a frequency bin (nfreq is the fastest axis of X: a wave's load of one channel is
-// 64 consecutive complex128, 16 B per lane), so the update at a bin never crosses lanes.  A
-// workgroup owns 64 bins of a 16 x 16 block of channel pairs (block row <= block column); its
-// 16 waves form a 4 x 4 grid and every lane keeps a 4 x 4 tile of complex sums in registers
-// (64 VGPRs), walking the segments in order from the stored sum -- so the result does not
-// depend on where the stream is cut into pushes, and nothing is atomic.  Per segment the
-// workgroup needs 16 + 16 channel rows of 64 bins (32 KB): wave w fetches rows w of both sets
-// (coalesced, once per workgroup instead of once per wave that uses them) one segment ahead
-// of the arithmetic into registers, and hands them over through a double-buffered LDS stage,
-// one barrier per segment.  Every wave then reads its 4 + 4 rows back as ds_read_b128 of
-// consecutive lanes (conflict-free) for 16 complex multiply-adds = 64 FMAs.
-// Grid: x = triangular block index (fastest: the workgroups resident together work on the
-// same bins of different channel blocks and share the segment's rows in L2), y = bin block.
-__global__ void __launch_bounds__(kCrossThreads)
+// The tile skeleton of pair_tile.h as it is: a lane is a frequency bin (nfreq is the fastest
+// axis of X: a wave's load of one channel is 64 consecutive complex128, 16 B per lane) and keeps
+// one complex sum per pair, 64 VGPRs, so the workgroup can be 16 waves.  Per segment it stages
+// 16 + 16 channel rows of 64 bins (32 KB); every wave reads its 4 + 4 rows back as ds_read_b128
+// for 16 complex multiply-adds = 64 FMAs.
+// Grid: x = triangular block index, y = bin block.
+__global__ void __launch_bounds__(CrossTile::Threads)
 cross_accumulate_kernel(const cx *__restrict__ X, int nseg, int nch, int nfreq, cx *__restrict__ acc,
                         int nblk) {
-    __shared__ cx stage[2][2 * kCrossB][kWave];          // 64 KB
-    int bi = 0, p = blockIdx.x;
-    while (p >= nblk - bi) {                             // row bi of the triangle holds nblk - bi blocks
-        p -= nblk - bi;
-        ++bi;
-    }
-    const int bj = bi + p;
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    const int wi = w / kCrossW, wj = w % kCrossW;
+    using P = CrossTile;
+    __shared__ cx stage[2][2 * P::B][kWave];             // 64 KB
+    const PairBlock<P> blk(blockIdx.x, nblk, nch);
+    const int lane = blk.lane;
     const int f = blockIdx.y * kWave + lane;
     const bool inside = f < nfreq;
-    // the two rows this wave stages
-    const int ci = bi * kCrossB + w, cj = bj * kCrossB + w;
-    const bool li = inside && ci < nch, lj = inside && cj < nch;
+    // the rows this wave stages
     // (a uniform base that moves from segment to segment plus a 32-bit offset per lane)
     const int64_t seg = (int64_t)nch * nfreq;
-    const int oi = li ? ci * nfreq + f : 0, oj = lj ? cj * nfreq + f : 0;
-    // the 4 x 4 pairs this lane sums; on a diagonal block the waves below the diagonal rest
-    const int i0 = bi * kCrossB + wi * kCrossT, j0 = bj * kCrossB + wj * kCrossT;
-    const bool active = i0 < nch && j0 < nch && (bi != bj || wi <= wj);
+    int off[P::Rows];
+    bool have[P::Rows];
+#pragma unroll
+    for (int k = 0; k < P::Rows; ++k) {
+        const int c = blk.channel(k);
+        have[k] = inside && c < nch;
+        off[k] = have[k] ? c * nfreq + f : 0;
+    }
     const cx zero = {0.0, 0.0};
 
-    cx sum[kCrossT][kCrossT];
-#pragma unroll
-    for (int a = 0; a < kCrossT; ++a)
-#pragma unroll
-        for (int b = 0; b < kCrossT; ++b) {
-            const int i = i0 + a, j = j0 + b;
-            sum[a][b] = (active && inside && j < nch && i <= j) ? acc[((int64_t)i * nch + j) * nfreq + f] : zero;
-        }
+    cx sum[P::T][P::T];
+    blk.pairs(nch, inside, [&](int a, int b, bool mine, int i, int j) {
+        sum[a][b] = mine ? acc[pair_at(i, j, nch, nfreq, f)] : zero;
+    });
 
-    cx gi = li ? X[oi] : zero, gj = lj ? X[oj] : zero;
-    stage[0][w][lane] = gi;
-    stage[0][kCrossB + w][lane] = gj;
-    __syncthreads();
-    for (int s = 0; s < nseg; ++s) {
-        const int cur = s & 1;
-        const bool more = s + 1 < nseg;
-        if (more) {
-            X += seg;
-            gi = li ? X[oi] : zero;
-            gj = lj ? X[oj] : zero;
-        }
-        if (active) {
-            cx u[kCrossT], v[kCrossT];
+    cx g[P::Rows];
+    pair_walk(
+        nseg, blk.active,
+        [&](int s) {
+            const cx *x = X + s * seg;
 #pragma unroll
-            for (int a = 0; a < kCrossT; ++a) u[a] = stage[cur][wi * kCrossT + a][lane];
+            for (int k = 0; k < P::Rows; ++k) g[k] = have[k] ? x[off[k]] : zero;
+        },
+        [&](int buf) {
 #pragma unroll
-            for (int b = 0; b < kCrossT; ++b) v[b] = stage[cur][kCrossB + wj * kCrossT + b][lane];
+            for (int k = 0; k < P::Rows; ++k) stage[buf][blk.entry(k)][lane] = g[k];
+        },
+        [&](int cur) {
+            cx u[P::T], v[P::T];
 #pragma unroll
-            for (int a = 0; a < kCrossT; ++a)
+            for (int a = 0; a < P::T; ++a) u[a] = stage[cur][blk.slot_i(a)][lane];
 #pragma unroll
-                for (int b = 0; b < kCrossT; ++b) {
+            for (int b = 0; b < P::T; ++b) v[b] = stage[cur][blk.slot_j(b)][lane];
+#pragma unroll
+            for (int a = 0; a < P::T; ++a)
+#pragma unroll
+                for (int b = 0; b < P::T; ++b) {
                     // conj(u) v = (ur vr + ui vi) + i (ur vi - ui vr), four FMAs in a fixed order
                     double re = sum[a][b].x, im = sum[a][b].y;
                     re = __builtin_fma(u[a].x, v[b].x, re);
@@ -91,23 +73,11 @@ cross_accumulate_kernel(const cx *__restrict__ X, int nseg, int nch, int nfreq, 
                     sum[a][b].x = re;
                     sum[a][b].y = im;
                 }
-        }
-        if (more) {
-            stage[cur ^ 1][w][lane] = gi;
-            stage[cur ^ 1][kCrossB + w][lane] = gj;
-        }
-        __syncthreads();
-    }
+        });
 
-    if (active && inside) {
-#pragma unroll
-        for (int a = 0; a < kCrossT; ++a)
-#pragma unroll
-            for (int b = 0; b < kCrossT; ++b) {
-                const int i = i0 + a, j = j0 + b;
-                if (j < nch && i <= j) acc[((int64_t)i * nch + j) * nfreq + f] = sum[a][b];
-            }
-    }
+    blk.pairs(nch, inside, [&](int a, int b, bool mine, int i, int j) {
+        if (mine) acc[pair_at(i, j, nch, nfreq, f)] = sum[a][b];
+    });
 }
 
 // One (i <= j) pair per (blockIdx.z, blockIdx.y), a lane per bin; writes [i, j] and its mirror
@@ -118,27 +88,24 @@ cross_accumulate_kernel(const cx *__restrict__ X, int nseg, int nch, int nfreq, 
 // sums (the count, the scaling and the doubling cancel), real.
 __global__ void __launch_bounds__(256)
 cross_finish_kernel(const cx *acc, double count, int nch, int nfreq, int nfft_is_even, int mode, void *out) {
-    const int i = blockIdx.z, j = blockIdx.y;
-    if (i > j) return;
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= nfreq) return;
-    const int64_t ij = ((int64_t)i * nch + j) * nfreq + f, ji = ((int64_t)j * nch + i) * nfreq + f;
-    const cx s = acc[ij];
+    const PairBin p(nch, nfreq, nfft_is_even);
+    if (!p.valid) return;
+    const cx s = acc[p.ij];
     if (mode == OSZ_CROSS_SPECTRUM) {
-        const double sides = (f == 0 || (nfft_is_even && f == nfreq - 1)) ? 1.0 : 2.0;
+        const double sides = p.real_bin ? 1.0 : 2.0;
         cx *o = static_cast<cx *>(out);
-        cx v = {s.x / count * sides, i == j ? 0.0 : s.y / count * sides};
-        o[ij] = v;
-        if (i != j) {
+        cx v = {s.x / count * sides, p.i == p.j ? 0.0 : s.y / count * sides};
+        o[p.ij] = v;
+        if (p.i != p.j) {
             v.y = -v.y;
-            o[ji] = v;
+            o[p.ji] = v;
         }
     } else {
-        const double pi = acc[((int64_t)i * nch + i) * nfreq + f].x, pj = acc[((int64_t)j * nch + j) * nfreq + f].x;
+        const double pi = acc[p.ii].x, pj = acc[p.jj].x;
         double *o = static_cast<double *>(out);
         const double c = (s.x * s.x + s.y * s.y) / (pi * pj);
-        o[ij] = c;
-        o[ji] = c;
+        o[p.ij] = c;
+        o[p.ji] = c;
     }
 }
 
@@ -150,17 +117,17 @@ extern "C" {
 
 int osz_cross_accumulate(const void *X, int64_t nseg, int nch, int nfreq, void *acc, void *stream) {
     OSZ_REQUIRE(X && acc, "osz_cross_accumulate: null argument");
-    OSZ_REQUIRE(nch >= 1 && nch <= 65535 && nfreq >= 1 && nseg >= 0 && nseg <= INT32_MAX &&
-                    (int64_t)nch * nfreq < ((int64_t)1 << 27),
+    int64_t nblk, tri;
+    if (int rc = pair_grid("osz_cross_accumulate", nch, CrossTile::B, &nblk, &tri)) return rc;
+    OSZ_REQUIRE(nfreq >= 1 && nseg >= 0 && nseg <= INT32_MAX && (int64_t)nch * nfreq < ((int64_t)1 << 27),
                 "osz_cross_accumulate: bad sizes (nch * nfreq must stay below 2^27)");
     OSZ_REQUIRE(((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(acc)) & 15) == 0,
                 "osz_cross_accumulate: X and acc must be 16-byte aligned");
     if (nseg == 0) return OSZ_OK;
-    const int64_t nblk = (nch + kCrossB - 1) / kCrossB;
-    const int64_t tri = nblk * (nblk + 1) / 2, fblk = ((int64_t)nfreq + kWave - 1) / kWave;
-    OSZ_REQUIRE(tri <= INT32_MAX && fblk <= 65535, "osz_cross_accumulate: grid too large");
+    const int64_t fblk = ((int64_t)nfreq + kWave - 1) / kWave;
+    OSZ_REQUIRE(fblk <= 65535, "osz_cross_accumulate: grid too large");
     KernelTimer timer("cross_accumulate", as_stream(stream));
-    hipLaunchKernelGGL(cross_accumulate_kernel, dim3((unsigned)tri, (unsigned)fblk), dim3(kCrossThreads), 0,
+    hipLaunchKernelGGL(cross_accumulate_kernel, dim3((unsigned)tri, (unsigned)fblk), dim3(CrossTile::Threads), 0,
                        as_stream(stream), static_cast<const cx *>(X), (int)nseg, nch, nfreq,
                        static_cast<cx *>(acc), (int)nblk);
     OSZ_HIP(hipGetLastError());

@@ -4,72 +4,54 @@
 // contribution) and adds d_s = theta_(s) - theta and d_s^2 in segment order, and the finishing
 // pass se = sqrt((N - 1) / N (sum d^2 - (sum d)^2 / N)) with its fixed points.  DESIGN.md
 // section 3, K12.
-#include "common.h"
+#include "pair_tile.h"
 
 namespace osz {
 
-typedef double cx __attribute__((ext_vector_type(2)));   // (re, im) of one complex128
+// K11's workgroup: 2 x 2 waves, an 8 x 8 block of pairs, wave w stages rows 4w .. 4w + 3 of the list
+using JackTile = PairTile<2, 1, false>;
+constexpr int kJackT = JackTile::T, kJackB = JackTile::B, kJackRows = JackTile::Rows;
 
-constexpr int kJackT = 4;                     // channels per side of a lane's register tile
-constexpr int kJackW = 2;                     // waves per side of a workgroup's tile
-constexpr int kJackB = kJackT * kJackW;       // channels per side of a workgroup's tile (8)
-constexpr int kJackWaves = kJackW * kJackW;   // 4
-constexpr int kJackThreads = kWave * kJackWaves;          // 256
-constexpr int kJackRows = 2 * kJackB / kJackWaves;        // rows a wave stages per segment (4)
-
-// sign(d) as lag_accumulate_kernel adds it: +-0 gives 0 (d itself), NaN gives NaN
-__device__ __forceinline__ double sign_of(double d) { return d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : d); }
-
-// The structure of lag_accumulate_kernel (phaseconn.hip): a lane is a frequency bin, a lane keeps
-// a 4 x 4 tile of pairs in registers, a workgroup of 4 waves (2 x 2) owns 64 bins of an 8 x 8
-// block of pairs (block row <= block column), wave w fetches rows 4w .. 4w + 3 of the 8 + 8
-// channel rows of a segment one segment ahead into registers and hands them over through a
-// double-buffered LDS stage, one barrier per segment.  Per pair the lane holds the totals the
+// The tile shape of pair_tile.h, a lane a frequency bin, with the walk and the tile loops written
+// out: five of the six instances hold 256 VGPRs and more in AGPRs at one wave per SIMD, where
+// the compiler's schedule decides their speed, and on pair_walk / PairBlock::pairs four of them
+// ran 1.3 to 3.7 % slower (profiles/pair_tile_ab.txt).  Per pair the lane holds the totals the
 // measure reads (1 to 3 doubles), theta from all segments and the two running sums, loaded from
-// dev2 at the start and stored at the end: the segments are walked in order from the stored
-// sums, nothing is atomic.  One measure per launch, MODE a template argument, so a launch
-// carries only its own registers (4 to 6 doubles per pair).
+// dev2 at the start and stored at the end.  One measure per launch, MODE a template argument, so
+// a launch carries only its own registers (4 to 6 doubles per pair).
 // coherence / imcoh: the staging wave also stages, next to each row, 1 / (P_c - |X_c|^2)
 // (coherence) or its square root (imcoh), P_c = Re acc[c, c] -- one division (and one square
 // root) per (channel, segment, bin) instead of one per (pair, segment, bin); the pair loop
 // multiplies.  theta is formed by the same expression as theta_(s), with nothing taken away.
 // plv reads spectra that osz_unit_phasors normalised and the sums of K10 over those.
-// d = Im(conj(u) v) is the expression of lag_accumulate_kernel, fma(ur, vi, -(ui vr)).
-// Grid: x = triangular block index (fastest), y = bin block.
+// d = Im(conj(u) v) is pair_im, the expression of lag_accumulate_kernel.
+// Grid: x = triangular block index, y = bin block.
 template <int MODE>
-__global__ void __launch_bounds__(kJackThreads)
+__global__ void __launch_bounds__(JackTile::Threads)
 jackknife_accumulate_kernel(const cx *__restrict__ X, int nseg, int nch, int nfreq, const cx *__restrict__ csum,
                             const double *__restrict__ lag, double count, double *__restrict__ dev2, int nblk) {
     constexpr bool kPower = MODE == OSZ_JACK_COHERENCE || MODE == OSZ_JACK_IMCOH;
     constexpr bool kComplex = MODE == OSZ_JACK_COHERENCE || MODE == OSZ_JACK_PLV;      // both parts of z
     __shared__ cx stage[2][2 * kJackB][kWave];                                          // 32 KB
     __shared__ double aux[kPower ? 2 : 1][kPower ? 2 * kJackB : 1][kPower ? kWave : 1]; // 16 KB
-    int bi = 0, p = blockIdx.x;
-    while (p >= nblk - bi) {                             // row bi of the triangle holds nblk - bi blocks
-        p -= nblk - bi;
-        ++bi;
-    }
-    const int bj = bi + p;
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    const int wi = w / kJackW, wj = w % kJackW;
+    const PairBlock<JackTile> blk(blockIdx.x, nblk, nch);
+    const int lane = blk.lane, i0 = blk.i0, j0 = blk.j0;
+    const bool active = blk.active;
     const int f = blockIdx.y * kWave + lane;
     const bool inside = f < nfreq;
-    // the rows this wave stages: entries 0 .. 7 of the list are block row bi's channels, 8 .. 15 bj's
+    // the rows this wave stages
     const int64_t seg = (int64_t)nch * nfreq;
     int off[kJackRows];
     bool have[kJackRows];
     double own[kJackRows];                               // P_c of the staged rows (coherence, imcoh)
 #pragma unroll
     for (int k = 0; k < kJackRows; ++k) {
-        const int r = w * kJackRows + k;
-        const int c = r < kJackB ? bi * kJackB + r : bj * kJackB + r - kJackB;
+        const int c = blk.channel(k);
         have[k] = inside && c < nch;
         off[k] = have[k] ? c * nfreq + f : 0;
         own[k] = 0.0;
-        if constexpr (kPower) own[k] = have[k] ? csum[((int64_t)c * nch + c) * nfreq + f].x : 0.0;
+        if constexpr (kPower) own[k] = have[k] ? csum[pair_at(c, c, nch, nfreq, f)].x : 0.0;
     }
-    const int i0 = bi * kJackB + wi * kJackT, j0 = bj * kJackB + wj * kJackT;
-    const bool active = i0 < nch && j0 < nch && (bi != bj || wi <= wj);
     const int64_t plane = (int64_t)nch * nch * nfreq;
     const cx zero = {0.0, 0.0};
     const double rn = 1.0 / count, rn1 = 1.0 / (count - 1.0);
@@ -134,12 +116,11 @@ jackknife_accumulate_kernel(const cx *__restrict__ X, int nseg, int nch, int nfr
         }
 
     cx g[kJackRows];
-    double ga[kJackRows];
 #pragma unroll
     for (int k = 0; k < kJackRows; ++k) {
         g[k] = have[k] ? X[off[k]] : zero;
-        stage[0][w * kJackRows + k][lane] = g[k];
-        if constexpr (kPower) aux[0][w * kJackRows + k][lane] = beside(own[k], g[k]);
+        stage[0][blk.entry(k)][lane] = g[k];
+        if constexpr (kPower) aux[0][blk.entry(k)][lane] = beside(own[k], g[k]);
     }
     __syncthreads();
     for (int s = 0; s < nseg; ++s) {
@@ -155,22 +136,21 @@ jackknife_accumulate_kernel(const cx *__restrict__ X, int nseg, int nch, int nfr
             double ru[kJackT], rv[kJackT];
 #pragma unroll
             for (int a = 0; a < kJackT; ++a) {
-                u[a] = stage[cur][wi * kJackT + a][lane];
-                v[a] = stage[cur][kJackB + wj * kJackT + a][lane];
+                u[a] = stage[cur][blk.slot_i(a)][lane];
+                v[a] = stage[cur][blk.slot_j(a)][lane];
                 ru[a] = rv[a] = 0.0;
                 if constexpr (kPower) {
-                    ru[a] = aux[cur][wi * kJackT + a][lane];
-                    rv[a] = aux[cur][kJackB + wj * kJackT + a][lane];
+                    ru[a] = aux[cur][blk.slot_i(a)][lane];
+                    rv[a] = aux[cur][blk.slot_j(a)][lane];
                 }
             }
 #pragma unroll
             for (int a = 0; a < kJackT; ++a)
 #pragma unroll
                 for (int b = 0; b < kJackT; ++b) {
-                    // Im(conj(u) v) = ur vi - ui vr: one product rounded, one fused (as K11 sums it)
-                    const double d = __builtin_fma(u[a].x, v[b].y, -(u[a].y * v[b].x));
+                    const double d = pair_im(u[a], v[b]);            // (as K11 sums it)
                     double re = 0.0;
-                    if constexpr (kComplex) re = __builtin_fma(u[a].x, v[b].x, u[a].y * v[b].y);
+                    if constexpr (kComplex) re = pair_re(u[a], v[b]);
                     double left;                                     // theta without segment s
                     if constexpr (MODE == OSZ_JACK_COHERENCE) {
                         const double ar = t0[a][b] - re, ai = t1[a][b] - d;
@@ -199,8 +179,8 @@ jackknife_accumulate_kernel(const cx *__restrict__ X, int nseg, int nch, int nfr
         if (more) {
 #pragma unroll
             for (int k = 0; k < kJackRows; ++k) {
-                stage[cur ^ 1][w * kJackRows + k][lane] = g[k];
-                if constexpr (kPower) aux[cur ^ 1][w * kJackRows + k][lane] = beside(own[k], g[k]);
+                stage[cur ^ 1][blk.entry(k)][lane] = g[k];
+                if constexpr (kPower) aux[cur ^ 1][blk.entry(k)][lane] = beside(own[k], g[k]);
             }
         }
         __syncthreads();
@@ -213,7 +193,7 @@ jackknife_accumulate_kernel(const cx *__restrict__ X, int nseg, int nch, int nfr
             for (int b = 0; b < kJackT; ++b) {
                 const int i = i0 + a, j = j0 + b;
                 if (j < nch && i <= j) {
-                    const int64_t at = ((int64_t)i * nch + j) * nfreq + f;
+                    const int64_t at = pair_at(i, j, nch, nfreq, f);
                     dev2[at] = s1[a][b];
                     dev2[plane + at] = s2[a][b];
                 }
@@ -230,27 +210,21 @@ jackknife_accumulate_kernel(const cx *__restrict__ X, int nseg, int nch, int nfr
 __global__ void __launch_bounds__(256)
 jackknife_finish_kernel(int mode, const double *dev2, const cx *csum, const double *lag, double count, int nch,
                         int nfreq, int nfft_is_even, double *out) {
-    const int i = blockIdx.z, j = blockIdx.y;
-    if (i > j) return;
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= nfreq) return;
-    const int64_t ij = ((int64_t)i * nch + j) * nfreq + f, ji = ((int64_t)j * nch + i) * nfreq + f;
-    const int64_t ii = ((int64_t)i * nch + i) * nfreq + f, jj = ((int64_t)j * nch + j) * nfreq + f;
-    const int64_t plane = (int64_t)nch * nch * nfreq;
-    const bool real_bin = f == 0 || (nfft_is_even && f == nfreq - 1);
+    const PairBin p(nch, nfreq, nfft_is_even);
+    if (!p.valid) return;
     const bool on_lag = mode >= OSZ_JACK_PLI;
-    const double own_i = on_lag ? lag[ii] : csum[ii].x, own_j = on_lag ? lag[jj] : csum[jj].x;
-    const double sum = dev2[ij], squares = dev2[plane + ij];
+    const double own_i = on_lag ? lag[p.ii] : csum[p.ii].x, own_j = on_lag ? lag[p.jj] : csum[p.jj].x;
+    const double sum = dev2[p.ij], squares = dev2[p.plane + p.ij];
     // sum d^2 - (sum d)^2 / N carries up to (3 N + 1) roundings of sum d^2: what does not exceed
     // them is the 0 of deviations that are equal to within rounding (and a negative value is)
     double v = squares - sum * sum / count;
     v = v <= 4.0 * count * 0x1p-53 * squares ? 0.0 : v;              // (false for a NaN: it stays)
     v = sqrt((count - 1.0) / count * v);
     if (own_i != own_i || own_j != own_j) v = __builtin_nan("");
-    else if (i == j) v = 0.0;
-    else if (real_bin && mode != OSZ_JACK_PLV) v = 0.0;
-    out[ij] = v;
-    if (i != j) out[ji] = v;
+    else if (p.i == p.j) v = 0.0;
+    else if (p.real_bin && mode != OSZ_JACK_PLV) v = 0.0;
+    out[p.ij] = v;
+    if (p.i != p.j) out[p.ji] = v;
 }
 
 static const char *jack_reads(int mode) {
@@ -269,8 +243,9 @@ int osz_jackknife_accumulate(int mode, const void *X, int64_t nseg, int nch, int
     const void *csum = mode <= OSZ_JACK_IMCOH ? acc : accn;
     const void *sums = mode <= OSZ_JACK_PLV ? csum : static_cast<const void *>(lag);
     OSZ_REQUIRE(X && sums && dev2, "osz_jackknife_accumulate: null argument (mode %d reads %s)", mode, jack_reads(mode));
-    OSZ_REQUIRE(nch >= 1 && nch <= 65535 && nfreq >= 1 && nseg >= 0 && nseg <= INT32_MAX &&
-                    (int64_t)nch * nfreq < ((int64_t)1 << 27),
+    int64_t nblk, tri;
+    if (int rc = pair_grid("osz_jackknife_accumulate", nch, JackTile::B, &nblk, &tri)) return rc;
+    OSZ_REQUIRE(nfreq >= 1 && nseg >= 0 && nseg <= INT32_MAX && (int64_t)nch * nfreq < ((int64_t)1 << 27),
                 "osz_jackknife_accumulate: bad sizes (nch * nfreq must stay below 2^27)");
     OSZ_REQUIRE(count >= 2 && nseg <= count, "osz_jackknife_accumulate: the totals must be those of at least two "
                                              "segments and of no fewer than this push holds");
@@ -279,11 +254,10 @@ int osz_jackknife_accumulate(int mode, const void *X, int64_t nseg, int nch, int
     OSZ_REQUIRE(((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(dev2)) & 15) == 0,
                 "osz_jackknife_accumulate: X, the totals and dev2 must be 16-byte aligned");
     if (nseg == 0) return OSZ_OK;
-    const int64_t nblk = (nch + kJackB - 1) / kJackB;
-    const int64_t tri = nblk * (nblk + 1) / 2, fblk = ((int64_t)nfreq + kWave - 1) / kWave;
-    OSZ_REQUIRE(tri <= INT32_MAX && fblk <= 65535, "osz_jackknife_accumulate: grid too large");
+    const int64_t fblk = ((int64_t)nfreq + kWave - 1) / kWave;
+    OSZ_REQUIRE(fblk <= 65535, "osz_jackknife_accumulate: grid too large");
     KernelTimer timer("jackknife_accumulate", as_stream(stream));
-    const dim3 grid((unsigned)tri, (unsigned)fblk), block(kJackThreads);
+    const dim3 grid((unsigned)tri, (unsigned)fblk), block(JackTile::Threads);
     const cx *x = static_cast<const cx *>(X), *c = static_cast<const cx *>(csum);
 #define OSZ_JACK_LAUNCH(M)                                                                                        \
     case M:                                                                                                       \

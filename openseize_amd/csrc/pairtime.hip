@@ -14,17 +14,11 @@
 // that order; the 64 lanes are then reduced in the fixed order of wave_sum63 and the block's
 // partial is written, nothing is atomic.  pair_fold_kernel adds the partials to the totals in
 // block order.  The sums therefore do not depend on how the stream is cut into pushes.
-#include "common.h"
+#include "pair_tile.h"
 
 namespace osz {
 
-typedef double cx __attribute__((ext_vector_type(2)));   // (re, im) of one complex128
-
-constexpr int kPtT = 4;                       // channels per side of a lane's register tile
-constexpr int kPtW = 2;                       // waves per side of a workgroup's tile
-constexpr int kPtB = kPtT * kPtW;             // channels per side of a workgroup's tile (8)
-constexpr int kPtWaves = kPtW * kPtW;         // 4
-constexpr int kPtThreads = kWave * kPtWaves;  // 256
+constexpr int kPtWaves = 4;                   // waves of a workgroup, of either kernel
 constexpr int kPtBlock = OSZ_ANALYTIC_BLOCK;  // samples per time block
 constexpr int kPtPlanes = 6;                  // prepared planes: x, y, r, a, ux, uy
 constexpr int kPtChan = 3;                    // per-channel sums: a, a^2, |u|^2
@@ -89,96 +83,82 @@ pair_prepare_kernel(const cx *__restrict__ z, int64_t ld, int nch, int64_t n, do
     }
 }
 
-// K11's structure turned onto the time axis: a lane keeps a 4 x 4 tile of pairs with ns sums
-// each, the workgroup is 2 x 2 waves (an 8 x 8 block of pairs, block row <= block column; 256
-// threads, so a wave may hold 512 registers -- ORTH keeps 80 doubles of sums).  Per 64-sample
-// step the workgroup needs nv planes of 8 + 8 channel rows: wave w fetches its quarter of that
-// list (coalesced, 8 B per lane) one step ahead of the arithmetic into registers and hands it
-// over through a double-buffered LDS stage, one barrier per step.  d comes from ONE expression,
-// fma(x_i, y_j, -(y_i x_j)), in ORTH and in LAG: their sums of m carry the same bits.
+// K11's workgroup (2 x 2 waves, an 8 x 8 block of pairs; 256 threads, so a wave may hold 512
+// registers -- ORTH keeps 80 doubles of sums) whose staged rows carry the group's nv planes;
+// wave w stages its quarter of the list, 8 B per lane
+template <int G> using PtTile = PairTile<2, PtGroup<G>::nv, false>;
+
+// The tile skeleton of pair_tile.h turned onto the time axis: a lane is a sample of a 64-sample
+// step and keeps ns sums per pair; the 64 lanes are reduced at the end.  d comes from ONE
+// expression, pair_im, in ORTH and in LAG: their sums of m carry the same bits.
 // Samples past the end of a short last block are staged as 0 and add +0.0.
-// Grid: x = triangular block index (fastest), y = time block.
+// Grid: x = triangular block index, y = time block.
 template <int G>
-__global__ void __launch_bounds__(kPtThreads)
+__global__ void __launch_bounds__(PtTile<G>::Threads)
 pair_accumulate_kernel(const double *__restrict__ prep, int nch, int64_t n, double *__restrict__ part, int nblk,
                        int nplanes, int plane0) {
-    constexpr int NV = PtGroup<G>::nv, NS = PtGroup<G>::ns;
-    constexpr int kRows = 2 * kPtB * NV / kPtWaves;      // staged rows per wave and step
-    __shared__ double stage[2][2 * kPtB * NV][kWave];    // ORTH: 48 KB
-    int bi = 0, p = blockIdx.x;
-    while (p >= nblk - bi) {                             // row bi of the triangle holds nblk - bi blocks
-        p -= nblk - bi;
-        ++bi;
-    }
-    const int bj = bi + p;
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    const int wi = w / kPtW, wj = w % kPtW;
+    using P = PtTile<G>;
+    constexpr int NV = P::NV, NS = PtGroup<G>::ns;
+    __shared__ double stage[2][2 * P::B * NV][kWave];    // ORTH: 48 KB
+    const PairBlock<P> blk(blockIdx.x, nblk, nch);
+    const int lane = blk.lane;
     const int64_t t0 = (int64_t)blockIdx.y * kPtBlock;
     const int64_t left = n - t0;                         // >= 1 by the grid
     const int here = left < kPtBlock ? (int)left : kPtBlock;
     const int nsteps = (here + kWave - 1) / kWave;
     const int64_t plane = (int64_t)nch * n;
-    // the rows this wave stages: entry e of the list is value e % NV of channel slot e / NV,
-    // slots 0 .. 7 block row bi's channels, 8 .. 15 bj's
-    const double *src[kRows];
-    bool have[kRows];
+    // the rows this wave stages
+    const double *src[P::Rows];
+    bool have[P::Rows];
 #pragma unroll
-    for (int k = 0; k < kRows; ++k) {
-        const int e = w * kRows + k, r = e / NV, v = e % NV;
-        const int c = r < kPtB ? bi * kPtB + r : bj * kPtB + r - kPtB;
+    for (int k = 0; k < P::Rows; ++k) {
+        const int c = blk.channel(k);
         have[k] = c < nch;
-        src[k] = prep + (PtGroup<G>::first + v) * plane + (have[k] ? (int64_t)c * n : 0) + t0 + lane;
+        src[k] = prep + (PtGroup<G>::first + blk.value(k)) * plane + (have[k] ? (int64_t)c * n : 0) + t0 + lane;
     }
-    const int i0 = bi * kPtB + wi * kPtT, j0 = bj * kPtB + wj * kPtT;
-    const bool active = i0 < nch && j0 < nch && (bi != bj || wi <= wj);
 
-    double s[NS][kPtT][kPtT];
+    double s[NS][P::T][P::T];
 #pragma unroll
     for (int q = 0; q < NS; ++q)
 #pragma unroll
-        for (int a = 0; a < kPtT; ++a)
+        for (int a = 0; a < P::T; ++a)
 #pragma unroll
-            for (int b = 0; b < kPtT; ++b) s[q][a][b] = 0.0;
+            for (int b = 0; b < P::T; ++b) s[q][a][b] = 0.0;
 
-    double g[kRows];
+    double g[P::Rows];
+    pair_walk(
+        nsteps, blk.active,
+        [&](int st) {
+            const int at = st * kWave;
 #pragma unroll
-    for (int k = 0; k < kRows; ++k) {
-        g[k] = have[k] && lane < here ? src[k][0] : 0.0;
-        stage[0][w * kRows + k][lane] = g[k];
-    }
-    __syncthreads();
-    for (int st = 0; st < nsteps; ++st) {
-        const int cur = st & 1;
-        const bool more = st + 1 < nsteps;
-        if (more) {
-            const int at = (st + 1) * kWave;
+            for (int k = 0; k < P::Rows; ++k) g[k] = have[k] && at + lane < here ? src[k][at] : 0.0;
+        },
+        [&](int buf) {
 #pragma unroll
-            for (int k = 0; k < kRows; ++k) g[k] = have[k] && at + lane < here ? src[k][at] : 0.0;
-        }
-        if (active) {
-            double u[kPtT][NV], v[kPtT][NV];
+            for (int k = 0; k < P::Rows; ++k) stage[buf][blk.entry(k)][lane] = g[k];
+        },
+        [&](int cur) {
+            double u[P::T][NV], v[P::T][NV];
 #pragma unroll
-            for (int a = 0; a < kPtT; ++a)
+            for (int a = 0; a < P::T; ++a)
 #pragma unroll
-                for (int q = 0; q < NV; ++q) u[a][q] = stage[cur][(wi * kPtT + a) * NV + q][lane];
+                for (int q = 0; q < NV; ++q) u[a][q] = stage[cur][blk.slot_i(a) * NV + q][lane];
 #pragma unroll
-            for (int b = 0; b < kPtT; ++b)
+            for (int b = 0; b < P::T; ++b)
 #pragma unroll
-                for (int q = 0; q < NV; ++q) v[b][q] = stage[cur][(kPtB + wj * kPtT + b) * NV + q][lane];
+                for (int q = 0; q < NV; ++q) v[b][q] = stage[cur][blk.slot_j(b) * NV + q][lane];
 #pragma unroll
-            for (int a = 0; a < kPtT; ++a)
+            for (int a = 0; a < P::T; ++a)
 #pragma unroll
-                for (int b = 0; b < kPtT; ++b) {
+                for (int b = 0; b < P::T; ++b) {
                     if constexpr (G == OSZ_ANALYTIC_AMP) {
                         s[0][a][b] = __builtin_fma(u[a][0], v[b][0], s[0][a][b]);
                     } else if constexpr (G == OSZ_ANALYTIC_LOCK) {
-                        // conj(u_i) u_j: each part one product rounded, one fused
-                        const double re = __builtin_fma(u[a][0], v[b][0], u[a][1] * v[b][1]);
-                        const double im = __builtin_fma(u[a][0], v[b][1], -(u[a][1] * v[b][0]));
-                        s[0][a][b] += re;
-                        s[1][a][b] += im;
+                        // conj(u_i) u_j
+                        s[0][a][b] += pair_re(u[a][0], u[a][1], v[b][0], v[b][1]);
+                        s[1][a][b] += pair_im(u[a][0], u[a][1], v[b][0], v[b][1]);
                     } else {
-                        const double d = __builtin_fma(u[a][0], v[b][1], -(u[a][1] * v[b][0]));
+                        const double d = pair_im(u[a][0], u[a][1], v[b][0], v[b][1]);
                         const double m = __builtin_fabs(d);
                         if constexpr (G == OSZ_ANALYTIC_LAG) {
                             s[0][a][b] += d;
@@ -193,27 +173,17 @@ pair_accumulate_kernel(const double *__restrict__ prep, int nch, int64_t n, doub
                         }
                     }
                 }
-        }
-        if (more) {
-#pragma unroll
-            for (int k = 0; k < kRows; ++k) stage[cur ^ 1][w * kRows + k][lane] = g[k];
-        }
-        __syncthreads();
-    }
+        });
 
-    if (active) {
+    if (blk.active) {
         const int64_t cc = (int64_t)nch * nch;
         double *dst = part + ((int64_t)blockIdx.y * nplanes + plane0) * cc;
 #pragma unroll
         for (int q = 0; q < NS; ++q)
-#pragma unroll
-            for (int a = 0; a < kPtT; ++a)
-#pragma unroll
-                for (int b = 0; b < kPtT; ++b) {
-                    const double total = wave_sum63(s[q][a][b]);
-                    const int i = i0 + a, j = j0 + b;
-                    if (lane == kWave - 1 && j < nch && i <= j) dst[q * cc + (int64_t)i * nch + j] = total;
-                }
+            blk.pairs(nch, true, [&](int a, int b, bool mine, int i, int j) {
+                const double total = wave_sum63(s[q][a][b]);
+                if (lane == kWave - 1 && mine) dst[q * cc + (int64_t)i * nch + j] = total;
+            });
     }
 }
 
@@ -227,14 +197,6 @@ pair_fold_kernel(const double *__restrict__ part, int64_t nb, int64_t count, int
     double t = tot[k];
     for (int64_t b = 0; b < nb; ++b) t += part[b * count + k];
     tot[k] = t;
-}
-
-// Pearson r from the five sums over `cnt` samples; a zero variance gives what IEEE gives.
-__device__ __forceinline__ double pearson(double cnt, double sp, double sq, double spp, double sqq, double spq) {
-    const double cov = __builtin_fma(cnt, spq, -(sp * sq));
-    const double vp = __builtin_fma(cnt, spp, -(sp * sp));
-    const double vq = __builtin_fma(cnt, sqq, -(sq * sq));
-    return cov / (sqrt(vp) * sqrt(vq));
 }
 
 // One (i <= j) pair per thread; writes [i, j] and its mirror.  In this order: a channel one of
@@ -285,7 +247,7 @@ static int pt_group_of(int mode) {
 template <int G>
 static void pt_launch(const double *prep, int nch, int64_t n, double *part, int nblk, int groups, dim3 grid,
                       hipStream_t st) {
-    hipLaunchKernelGGL(pair_accumulate_kernel<G>, grid, dim3(kPtThreads), 0, st, prep, nch, n, part, nblk,
+    hipLaunchKernelGGL(pair_accumulate_kernel<G>, grid, dim3(PtTile<G>::Threads), 0, st, prep, nch, n, part, nblk,
                        pt_planes(groups), pt_first(groups, G));
 }
 
@@ -305,8 +267,9 @@ int osz_analytic_accumulate(const void *z, int64_t ld, int nch, int64_t n, int g
                             double *work, int64_t work_len, void *stream) {
     OSZ_REQUIRE(z && sums && chan && work, "osz_analytic_accumulate: null argument");
     OSZ_REQUIRE(groups >= 1 && groups <= OSZ_ANALYTIC_ALL, "osz_analytic_accumulate: unknown sum groups %d", groups);
-    OSZ_REQUIRE(nch >= 1 && nch <= 65535 && n >= 0 && ld >= n && n <= (int64_t)65535 * kPtBlock &&
-                    (int64_t)nch * n < ((int64_t)1 << 40),
+    int64_t nblk, tri;
+    if (int rc = pair_grid("osz_analytic_accumulate", nch, PtTile<OSZ_ANALYTIC_AMP>::B, &nblk, &tri)) return rc;
+    OSZ_REQUIRE(n >= 0 && ld >= n && n <= (int64_t)65535 * kPtBlock && (int64_t)nch * n < ((int64_t)1 << 40),
                 "osz_analytic_accumulate: bad sizes");
     OSZ_REQUIRE((reinterpret_cast<uintptr_t>(z) & 15) == 0 &&
                     ((reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(chan) |
@@ -317,10 +280,9 @@ int osz_analytic_accumulate(const void *z, int64_t ld, int nch, int64_t n, int g
                 (long long)work_len, (long long)osz_analytic_work(nch, n, groups));
     if (n == 0) return OSZ_OK;
     const int64_t nb = (n + kPtBlock - 1) / kPtBlock;
-    const int64_t nblk = (nch + kPtB - 1) / kPtB, tri = nblk * (nblk + 1) / 2;
     const int np = pt_planes(groups);
     const int64_t cc = (int64_t)nch * nch;
-    OSZ_REQUIRE(tri <= INT32_MAX && (np * cc + 255) / 256 <= INT32_MAX, "osz_analytic_accumulate: grid too large");
+    OSZ_REQUIRE((np * cc + 255) / 256 <= INT32_MAX, "osz_analytic_accumulate: grid too large");
     double *prep = work, *part = prep + kPtPlanes * (int64_t)nch * n, *cpart = part + nb * np * cc;
     hipStream_t st = as_stream(stream);
     {

@@ -3,133 +3,91 @@
 // sum sign d), the in-place normalisation X / |X| whose cross-spectra (K10's kernel) are the
 // phase-locking sums, and the finishing pass of imcoh / plv / pli / wpli / dwpli with their fixed
 // points.  DESIGN.md section 3, K11.
-#include "common.h"
+#include "pair_tile.h"
 
 namespace osz {
 
-typedef double cx __attribute__((ext_vector_type(2)));   // (re, im) of one complex128
+// 2 x 2 waves: an 8 x 8 block of pairs; wave w stages rows 4w .. 4w + 3 of the two sets taken as one list
+using LagTile = PairTile<2, 1, false>;
 
-constexpr int kLagT = 4;                      // channels per side of a lane's register tile
-constexpr int kLagW = 2;                      // waves per side of a workgroup's tile
-constexpr int kLagB = kLagT * kLagW;          // channels per side of a workgroup's tile (8)
-constexpr int kLagWaves = kLagW * kLagW;      // 4
-constexpr int kLagThreads = kWave * kLagWaves;            // 256
-constexpr int kLagRows = 2 * kLagB / kLagWaves;           // rows a wave stages per segment (4)
-
-// The structure of cross_accumulate_kernel (cross.hip) with four real sums per pair instead of
-// one complex one: a lane is a frequency bin, a lane keeps a 4 x 4 tile of pairs -- 64 doubles,
-// 128 VGPRs, which is why the workgroup is 4 waves (2 x 2: 64 bins of an 8 x 8 block of pairs,
-// block row <= block column) and not K10's 16: at 256 threads a wave may hold 512 registers and
-// several workgroups share a CU, each behind its own barrier.  Per segment the workgroup needs
-// 8 + 8 channel rows of 64 bins (16 KB): wave w fetches rows 4w .. 4w + 3 of the two sets taken
-// as one list (coalesced, 16 B per lane) one segment ahead of the arithmetic into registers and
-// hands them over through a double-buffered LDS stage, one barrier per segment; every wave reads
-// its 4 + 4 rows back as ds_read_b128 of consecutive lanes.  The segments are walked in order
-// from the stored sums, nothing is atomic: the sums do not depend on where the stream is cut.
-// d comes from ONE expression, fma(ur, vi, -(ui vr)), and all four sums are fed from it.  A NaN
-// d goes into all four (the sign of NaN is NaN here, not 0).
-// Grid: x = triangular block index (fastest), y = bin block.
-__global__ void __launch_bounds__(kLagThreads)
+// The tile skeleton of pair_tile.h with four real sums per pair instead of K10's one complex one:
+// a lane is a frequency bin and keeps 64 doubles, 128 VGPRs, which is why the workgroup is 4
+// waves and not K10's 16: at 256 threads a wave may hold 512 registers and several workgroups
+// share a CU, each behind its own barrier.  Per segment the workgroup stages 8 + 8 channel rows
+// of 64 bins (16 KB), 16 B per lane; every wave reads its 4 + 4 rows back as ds_read_b128.
+// d comes from ONE expression, pair_im, and all four sums are fed from it.  A NaN d goes into
+// all four (the sign of NaN is NaN here, not 0).
+// Grid: x = triangular block index, y = bin block.
+__global__ void __launch_bounds__(LagTile::Threads)
 lag_accumulate_kernel(const cx *__restrict__ X, int nseg, int nch, int nfreq, double *__restrict__ lag,
                       int nblk) {
-    __shared__ cx stage[2][2 * kLagB][kWave];            // 32 KB
-    int bi = 0, p = blockIdx.x;
-    while (p >= nblk - bi) {                             // row bi of the triangle holds nblk - bi blocks
-        p -= nblk - bi;
-        ++bi;
-    }
-    const int bj = bi + p;
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
-    const int wi = w / kLagW, wj = w % kLagW;
+    using P = LagTile;
+    __shared__ cx stage[2][2 * P::B][kWave];             // 32 KB
+    const PairBlock<P> blk(blockIdx.x, nblk, nch);
+    const int lane = blk.lane;
     const int f = blockIdx.y * kWave + lane;
     const bool inside = f < nfreq;
-    // the rows this wave stages: entries 0 .. 7 of the list are block row bi's channels, 8 .. 15 bj's
+    // the rows this wave stages
     const int64_t seg = (int64_t)nch * nfreq;
-    int off[kLagRows];
-    bool have[kLagRows];
+    int off[P::Rows];
+    bool have[P::Rows];
 #pragma unroll
-    for (int k = 0; k < kLagRows; ++k) {
-        const int r = w * kLagRows + k;
-        const int c = r < kLagB ? bi * kLagB + r : bj * kLagB + r - kLagB;
+    for (int k = 0; k < P::Rows; ++k) {
+        const int c = blk.channel(k);
         have[k] = inside && c < nch;
         off[k] = have[k] ? c * nfreq + f : 0;
     }
-    // the 4 x 4 pairs this lane sums; on a diagonal block the wave below the diagonal rests
-    const int i0 = bi * kLagB + wi * kLagT, j0 = bj * kLagB + wj * kLagT;
-    const bool active = i0 < nch && j0 < nch && (bi != bj || wi <= wj);
     const int64_t plane = (int64_t)nch * nch * nfreq;
     const cx zero = {0.0, 0.0};
 
-    double sd[kLagT][kLagT], sa[kLagT][kLagT], sq[kLagT][kLagT], sg[kLagT][kLagT];
-#pragma unroll
-    for (int a = 0; a < kLagT; ++a)
-#pragma unroll
-        for (int b = 0; b < kLagT; ++b) {
-            const int i = i0 + a, j = j0 + b;
-            const bool mine = active && inside && j < nch && i <= j;
-            const int64_t at = ((int64_t)i * nch + j) * nfreq + f;
-            sd[a][b] = mine ? lag[at] : 0.0;
-            sa[a][b] = mine ? lag[plane + at] : 0.0;
-            sq[a][b] = mine ? lag[2 * plane + at] : 0.0;
-            sg[a][b] = mine ? lag[3 * plane + at] : 0.0;
-        }
+    double sd[P::T][P::T], sa[P::T][P::T], sq[P::T][P::T], sg[P::T][P::T];
+    blk.pairs(nch, inside, [&](int a, int b, bool mine, int i, int j) {
+        const int64_t at = pair_at(i, j, nch, nfreq, f);
+        sd[a][b] = mine ? lag[at] : 0.0;
+        sa[a][b] = mine ? lag[plane + at] : 0.0;
+        sq[a][b] = mine ? lag[2 * plane + at] : 0.0;
+        sg[a][b] = mine ? lag[3 * plane + at] : 0.0;
+    });
 
-    cx g[kLagRows];
+    cx g[P::Rows];
+    pair_walk(
+        nseg, blk.active,
+        [&](int s) {
+            const cx *x = X + s * seg;
 #pragma unroll
-    for (int k = 0; k < kLagRows; ++k) {
-        g[k] = have[k] ? X[off[k]] : zero;
-        stage[0][w * kLagRows + k][lane] = g[k];
-    }
-    __syncthreads();
-    for (int s = 0; s < nseg; ++s) {
-        const int cur = s & 1;
-        const bool more = s + 1 < nseg;
-        if (more) {
-            X += seg;
+            for (int k = 0; k < P::Rows; ++k) g[k] = have[k] ? x[off[k]] : zero;
+        },
+        [&](int buf) {
 #pragma unroll
-            for (int k = 0; k < kLagRows; ++k) g[k] = have[k] ? X[off[k]] : zero;
-        }
-        if (active) {
-            cx u[kLagT], v[kLagT];
+            for (int k = 0; k < P::Rows; ++k) stage[buf][blk.entry(k)][lane] = g[k];
+        },
+        [&](int cur) {
+            cx u[P::T], v[P::T];
 #pragma unroll
-            for (int a = 0; a < kLagT; ++a) u[a] = stage[cur][wi * kLagT + a][lane];
+            for (int a = 0; a < P::T; ++a) u[a] = stage[cur][blk.slot_i(a)][lane];
 #pragma unroll
-            for (int b = 0; b < kLagT; ++b) v[b] = stage[cur][kLagB + wj * kLagT + b][lane];
+            for (int b = 0; b < P::T; ++b) v[b] = stage[cur][blk.slot_j(b)][lane];
 #pragma unroll
-            for (int a = 0; a < kLagT; ++a)
+            for (int a = 0; a < P::T; ++a)
 #pragma unroll
-                for (int b = 0; b < kLagT; ++b) {
-                    // Im(conj(u) v) = ur vi - ui vr: one product rounded, one fused
-                    const double t = u[a].y * v[b].x;
-                    const double d = __builtin_fma(u[a].x, v[b].y, -t);
+                for (int b = 0; b < P::T; ++b) {
+                    const double d = pair_im(u[a], v[b]);
                     sd[a][b] += d;
                     sa[a][b] += __builtin_fabs(d);
                     sq[a][b] = __builtin_fma(d, d, sq[a][b]);
-                    sg[a][b] += d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : d);      // (+-0 adds 0, NaN adds NaN)
+                    sg[a][b] += sign_of(d);
                 }
-        }
-        if (more) {
-#pragma unroll
-            for (int k = 0; k < kLagRows; ++k) stage[cur ^ 1][w * kLagRows + k][lane] = g[k];
-        }
-        __syncthreads();
-    }
+        });
 
-    if (active && inside) {
-#pragma unroll
-        for (int a = 0; a < kLagT; ++a)
-#pragma unroll
-            for (int b = 0; b < kLagT; ++b) {
-                const int i = i0 + a, j = j0 + b;
-                if (j < nch && i <= j) {
-                    const int64_t at = ((int64_t)i * nch + j) * nfreq + f;
-                    lag[at] = sd[a][b];
-                    lag[plane + at] = sa[a][b];
-                    lag[2 * plane + at] = sq[a][b];
-                    lag[3 * plane + at] = sg[a][b];
-                }
-            }
-    }
+    blk.pairs(nch, inside, [&](int a, int b, bool mine, int i, int j) {
+        if (mine) {
+            const int64_t at = pair_at(i, j, nch, nfreq, f);
+            lag[at] = sd[a][b];
+            lag[plane + at] = sa[a][b];
+            lag[2 * plane + at] = sq[a][b];
+            lag[3 * plane + at] = sg[a][b];
+        }
+    });
 }
 
 // X <- X / |X|, one element per thread: 0 gives 0 / 0 = NaN, a NaN stays one.
@@ -151,39 +109,33 @@ __global__ void __launch_bounds__(256) unit_phasors_kernel(cx *X, int64_t n) {
 __global__ void __launch_bounds__(256)
 phase_finish_kernel(int mode, const cx *acc, const cx *accn, const double *lag, double count, int nch,
                     int nfreq, int nfft_is_even, double *out) {
-    const int i = blockIdx.z, j = blockIdx.y;
-    if (i > j) return;
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= nfreq) return;
-    const int64_t ij = ((int64_t)i * nch + j) * nfreq + f, ji = ((int64_t)j * nch + i) * nfreq + f;
-    const int64_t ii = ((int64_t)i * nch + i) * nfreq + f, jj = ((int64_t)j * nch + j) * nfreq + f;
-    const int64_t plane = (int64_t)nch * nch * nfreq;
-    const bool real_bin = f == 0 || (nfft_is_even && f == nfreq - 1);
+    const PairBin p(nch, nfreq, nfft_is_even);
+    if (!p.valid) return;
     double own_i, own_j, v;
     if (mode == OSZ_PHASE_IMCOH) {
-        own_i = acc[ii].x;
-        own_j = acc[jj].x;
-        v = acc[ij].y / sqrt(own_i * own_j);
+        own_i = acc[p.ii].x;
+        own_j = acc[p.jj].x;
+        v = acc[p.ij].y / sqrt(own_i * own_j);
     } else if (mode == OSZ_PHASE_PLV) {
-        own_i = accn[ii].x;
-        own_j = accn[jj].x;
-        const cx s = accn[ij];
+        own_i = accn[p.ii].x;
+        own_j = accn[p.jj].x;
+        const cx s = accn[p.ij];
         v = sqrt(s.x * s.x + s.y * s.y) / count;
     } else {
-        own_i = lag[ii];
-        own_j = lag[jj];
-        const double d = lag[ij], a = lag[plane + ij], q = lag[2 * plane + ij];
-        if (mode == OSZ_PHASE_PLI) v = __builtin_fabs(lag[3 * plane + ij]) / count;
+        own_i = lag[p.ii];
+        own_j = lag[p.jj];
+        const double d = lag[p.ij], a = lag[p.plane + p.ij], q = lag[2 * p.plane + p.ij];
+        if (mode == OSZ_PHASE_PLI) v = __builtin_fabs(lag[3 * p.plane + p.ij]) / count;
         else if (mode == OSZ_PHASE_WPLI) v = __builtin_fabs(d) / a;
         else v = (d * d - q) / (a * a - q);
     }
     bool fixed = true;
     if (own_i != own_i || own_j != own_j) v = __builtin_nan("");
-    else if (i == j) v = mode == OSZ_PHASE_PLV ? 1.0 : 0.0;
-    else if (real_bin && mode != OSZ_PHASE_PLV) v = 0.0;
+    else if (p.i == p.j) v = mode == OSZ_PHASE_PLV ? 1.0 : 0.0;
+    else if (p.real_bin && mode != OSZ_PHASE_PLV) v = 0.0;
     else fixed = false;
-    out[ij] = v;
-    if (i != j) out[ji] = (mode == OSZ_PHASE_IMCOH && !fixed) ? -v : v;
+    out[p.ij] = v;
+    if (p.i != p.j) out[p.ji] = (mode == OSZ_PHASE_IMCOH && !fixed) ? -v : v;
 }
 
 }  // namespace osz
@@ -194,17 +146,17 @@ extern "C" {
 
 int osz_lag_accumulate(const void *X, int64_t nseg, int nch, int nfreq, double *lag, void *stream) {
     OSZ_REQUIRE(X && lag, "osz_lag_accumulate: null argument");
-    OSZ_REQUIRE(nch >= 1 && nch <= 65535 && nfreq >= 1 && nseg >= 0 && nseg <= INT32_MAX &&
-                    (int64_t)nch * nfreq < ((int64_t)1 << 27),
+    int64_t nblk, tri;
+    if (int rc = pair_grid("osz_lag_accumulate", nch, LagTile::B, &nblk, &tri)) return rc;
+    OSZ_REQUIRE(nfreq >= 1 && nseg >= 0 && nseg <= INT32_MAX && (int64_t)nch * nfreq < ((int64_t)1 << 27),
                 "osz_lag_accumulate: bad sizes (nch * nfreq must stay below 2^27)");
     OSZ_REQUIRE(((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(lag)) & 15) == 0,
                 "osz_lag_accumulate: X and lag must be 16-byte aligned");
     if (nseg == 0) return OSZ_OK;
-    const int64_t nblk = (nch + kLagB - 1) / kLagB;
-    const int64_t tri = nblk * (nblk + 1) / 2, fblk = ((int64_t)nfreq + kWave - 1) / kWave;
-    OSZ_REQUIRE(tri <= INT32_MAX && fblk <= 65535, "osz_lag_accumulate: grid too large");
+    const int64_t fblk = ((int64_t)nfreq + kWave - 1) / kWave;
+    OSZ_REQUIRE(fblk <= 65535, "osz_lag_accumulate: grid too large");
     KernelTimer timer("lag_accumulate", as_stream(stream));
-    hipLaunchKernelGGL(lag_accumulate_kernel, dim3((unsigned)tri, (unsigned)fblk), dim3(kLagThreads), 0,
+    hipLaunchKernelGGL(lag_accumulate_kernel, dim3((unsigned)tri, (unsigned)fblk), dim3(LagTile::Threads), 0,
                        as_stream(stream), static_cast<const cx *>(X), (int)nseg, nch, nfreq, lag, (int)nblk);
     OSZ_HIP(hipGetLastError());
     return OSZ_OK;

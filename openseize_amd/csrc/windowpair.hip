@@ -16,11 +16,10 @@
 // Every sum has an order that is a function of W alone and nothing is atomic: an element of G is
 // the MFMA's k-ordered chain over its own two rows, one chain per sub-block counted from the
 // window's start; a row's sum is lane-strided and folded by wave_sum63.
-#include "common.h"
+#include "pair_tile.h"
 
 namespace osz {
 
-typedef double wp_cx __attribute__((ext_vector_type(2)));   // (re, im) of one complex128
 typedef double wp_d4 __attribute__((ext_vector_type(4)));   // one lane's share of a 16 x 16 tile
 
 constexpr int kWpBlock = OSZ_WC_BLOCK;        // samples per sub-block of a window
@@ -41,11 +40,11 @@ __host__ __device__ inline bool wp_lock(int mask) { return (mask & ((1 << OSZ_WC
 // a = |z|, u = z / a, once per sample: stage[0] = a, stage[1] = u_x, stage[2] = u_y, each (nch, n).
 // A zero sample gives u = 0 / 0 = NaN.  One thread per sample.
 __global__ void __launch_bounds__(256)
-window_stage_kernel(const wp_cx *__restrict__ z, int64_t ld, int nch, int64_t n, double *__restrict__ stage) {
+window_stage_kernel(const cx *__restrict__ z, int64_t ld, int nch, int64_t n, double *__restrict__ stage) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int c = blockIdx.y;
     if (t >= n) return;
-    const wp_cx v = z[(int64_t)c * ld + t];
+    const cx v = z[(int64_t)c * ld + t];
     const double a = hypot(v.x, v.y);
     const int64_t plane = (int64_t)nch * n, at = (int64_t)c * n + t;
     stage[at] = a;
@@ -93,12 +92,8 @@ __global__ void __launch_bounds__(kWpThreads)
 window_gram_kernel(const double *__restrict__ rows, int64_t ld, int nrows, int64_t W, int64_t step, int64_t win0,
                    int nblk, double *__restrict__ part) {
     __shared__ double tile[2 * kWpSide][kWpPitch];           // 67.6 KB: two workgroups per CU
-    int bi = 0, q = blockIdx.x;
-    while (q >= nblk - bi) {                                 // row bi of the triangle holds nblk - bi blocks
-        q -= nblk - bi;
-        ++bi;
-    }
-    const int bj = bi + q;
+    int bi, bj;
+    pair_triangle(blockIdx.x, nblk, &bi, &bj);
     const bool diag = bi == bj;
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
     const int wi = w >> 1, wj = w & 1;
@@ -183,14 +178,6 @@ window_gram_kernel(const double *__restrict__ rows, int64_t ld, int nrows, int64
         }
 }
 
-// Pearson r from the five sums over `cnt` samples; a zero variance gives what IEEE gives.
-__device__ __forceinline__ double wp_pearson(double cnt, double sp, double sq, double spp, double sqq, double spq) {
-    const double cov = __builtin_fma(cnt, spq, -(sp * sq));
-    const double vp = __builtin_fma(cnt, spp, -(sp * sp));
-    const double vq = __builtin_fma(cnt, sqq, -(sq * sq));
-    return cov / (sqrt(vp) * sqrt(vq));
-}
-
 // the sub-blocks' partials of G[i, j] of one window, added in sub-block order
 __device__ __forceinline__ double wp_fold(const double *__restrict__ g, int nsub, int64_t rr, int64_t at) {
     double t = g[at];
@@ -258,7 +245,7 @@ window_finish_kernel(const double *__restrict__ part, int nsub, const double *__
             ++plane;
         }
         if (mask & (1 << OSZ_WC_CORR)) {
-            double v = wp_pearson(cnt, si, sj, gii, gjj, gij);
+            double v = pearson(cnt, si, sj, gii, gjj, gij);
             v = v > 1.0 ? 1.0 : v < -1.0 ? -1.0 : v;         // (a NaN passes: a constant channel is 0 / 0)
             if (lost) v = __builtin_nan("");
             else if (i == j && v == v) v = 1.0;
@@ -267,7 +254,7 @@ window_finish_kernel(const double *__restrict__ part, int nsub, const double *__
             ++plane;
         }
         if (mask & (1 << OSZ_WC_AEC)) {
-            double v = wp_pearson(cnt, si, sj, gii, gjj, gij);
+            double v = pearson(cnt, si, sj, gii, gjj, gij);
             if (lost) v = __builtin_nan("");
             else if (i == j) v = 1.0;
             o[plane * out_plane + at] = v;
@@ -347,7 +334,7 @@ int osz_window_pairs(const void *x, int64_t pitch, int nch, int64_t n, int is_co
         KernelTimer timer("window_pair_prepare", st);
         if (is_complex)
             hipLaunchKernelGGL(window_stage_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)nch), dim3(256), 0, st,
-                               static_cast<const wp_cx *>(x), pitch, nch, n, stage);
+                               static_cast<const cx *>(x), pitch, nch, n, stage);
         hipLaunchKernelGGL(window_sums_kernel, dim3((unsigned)p.nwin, (unsigned)nch), dim3(kWave), 0, st, amp, ld, nch,
                            winsize, step, is_complex ? stage + plane : nullptr, is_complex ? stage + 2 * plane : nullptr,
                            chan);
