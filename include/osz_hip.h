@@ -1034,6 +1034,52 @@ int osz_window_pairs(const void *x, int64_t pitch, int nch, int64_t n, int is_co
                      int ddof, int mask, double *out, int64_t plane_pitch, double *work, int64_t work_len,
                      void *stream);
 
+/* ---- fractal dimensions and DFA per window (features/fractal.py window_fractal) ----------- */
+/* (csrc/windowfrac.hip, K20) */
+#define OSZ_WR_LONGEST 4096       /* the longest window: it is held in LDS, 32 KB                             */
+#define OSZ_WR_WIDE 512           /* windows of at least this many samples take 256 threads, shorter ones 64  */
+#define OSZ_WR_KMAX 64            /* the largest kmax of higuchi                                              */
+#define OSZ_WR_SCALES 32          /* the most scales of dfa: they travel in the kernel's arguments            */
+typedef enum {
+    OSZ_WR_HIGUCHI = 0,           /* slope of ln L(k) on ln(1 / k), Higuchi 1988                           */
+    OSZ_WR_KATZ = 1,              /* ln n / (ln n + ln(d / L)), Katz 1988                                  */
+    OSZ_WR_PETROSIAN = 2,         /* log10 W / (log10 W + log10(W / (W + 0.4 N))), Petrosian 1995          */
+    OSZ_WR_DFA = 3,               /* slope of ln F(n) on ln n, detrended fluctuation analysis              */
+    OSZ_WR_DFA_FLUCTUATIONS = 4,  /* the F(n) themselves, one plane per scale                              */
+    OSZ_WR_COUNT = 5
+} osz_window_fractal_measure;
+/*
+ * x, the windows, mask (bit 1 << e of an osz_window_fractal_measure) and out are those of
+ * osz_window_features: out[p * plane_pitch + c * row_pitch + win0 + k], p the plane's rank among
+ * those present -- higuchi, katz, petrosian, dfa and then the nscales planes of dfa_fluctuations;
+ * nothing else of out is touched.  With x_0 .. x_{W-1} one window, W = winsize:
+ *   higuchi    for k = 1 .. kmax and m = 0 .. k - 1: n_mk = floor((W - 1 - m) / k),
+ *              L_m(k) = (sum_{i=1..n_mk} |x_{m+ik} - x_{m+(i-1)k}|) (W - 1) / (n_mk k) / k, L(k) the
+ *              mean of L_m(k) over m; the result is the least-squares slope of v = ln L(k) on u =
+ *              ln(1 / k) with the abscissa centred, sum (u - mean u) v / sum (u - mean u)^2.  An
+ *              L(k) = 0 gives NaN.
+ *   katz       L = sum |x_{i+1} - x_i|, d = max_i |x_i - x_0|, n = W - 1: ln n / (ln n + ln(d / L));
+ *              a constant window gives NaN.
+ *   petrosian  N the number of i with d_i = x_{i+1} - x_i and d_{i+1} of strictly opposite sign (a
+ *              zero difference is no sign): log10 W / (log10 W + log10(W / (W + 0.4 N))).
+ *   dfa        y_t = sum_{j<=t} (x_j - mean), the mean from sums about x_0.  For each scale n the
+ *              floor(W / n) boxes of n samples counted from the window's first sample (the tail is
+ *              dropped); in each box the least-squares line of y about the box's first value;
+ *              F(n) = sqrt(mean over all boxed samples of the squared residual).  The result is the
+ *              slope of ln F(n) on ln n, centred as above; an F(n) = 0 gives NaN.
+ *   dfa_fluctuations  F(n), plane s that of scales[s].
+ * scales: nscales ints in HOST memory, read only when a dfa measure is asked: 2 <= nscales <=
+ * OSZ_WR_SCALES, strictly increasing, 4 <= n <= winsize / 2.  8 <= winsize <= OSZ_WR_LONGEST, 2 <=
+ * kmax <= OSZ_WR_KMAX and winsize >= 2 kmax when higuchi is asked.
+ * A window that holds a NaN or +-inf is NaN in every plane.  A window's bits depend on winsize,
+ * kmax, scales and its own samples only: every sum runs in an order that is a function of
+ * (winsize, k) or (winsize, n) alone, the count of petrosian is an integer, and no floating-point
+ * operation is atomic.  One launch, one workgroup per window, no work space.
+ */
+int osz_window_fractal(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step,
+                       int mask, int kmax, const int *scales, int nscales, double *out, int64_t plane_pitch,
+                       int64_t row_pitch, int64_t win0, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

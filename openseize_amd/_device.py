@@ -1478,7 +1478,7 @@ def bispec_finish(mode, count, k_lo, sums, power):
 
 def name_mask(table, names):
     """The bit mask a kernel takes for ``names``, keys of ``table``: one of _lib.WINDOW_FEATURE,
-    WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL and WINDOW_CONNECTIVITY, name -> bit."""
+    WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL, WINDOW_CONNECTIVITY and WINDOW_FRACTAL, name -> bit."""
     mask = 0
     for name in names:
         mask |= 1 << table[name]
@@ -1543,6 +1543,30 @@ def window_entropy(x2d, winsize, step, mask, m, r, tolerance, order, delay, norm
                                           int(step), int(mask), int(m), float(r), _lib.WE_TOLERANCE[tolerance],
                                           int(order), int(delay), int(bool(normalize)), ptr(out), out.stride(0),
                                           out.stride(1), int(win0), stream_ptr()))
+    return nwin
+
+
+def window_fractal(x2d, winsize, step, mask, kmax, scales, out, win0=0):
+    """osz_window_fractal: the measures in the bit mask ``mask`` of every window of ``winsize``
+    samples, ``step`` apart, that x2d -- (nch, n) float64 CUDA rows, unit stride along n -- holds,
+    written to out[p, c, win0 + k]: out a contiguous float64 (planes, nch, room) CUDA tensor whose
+    planes are, of those asked and in the order of _lib.WINDOW_FRACTAL, higuchi, katz, petrosian,
+    dfa and one per value of ``scales`` for dfa_fluctuations (a sequence of ints, read only with a
+    dfa bit set).  Returns the number of windows written per row."""
+    lib = require_gpu()
+    nch, n = _window_rows("window_fractal", x2d)
+    nwin = lib.osz_window_count(n, int(winsize), int(step))
+    if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_FRACTAL):
+        raise ValueError(f"window_fractal: bad sizes or measure mask ({n}, {winsize}, {step}, {mask})")
+    wr = _lib.WINDOW_FRACTAL
+    ns = [int(s) for s in scales] if mask & (1 << wr["dfa"] | 1 << wr["dfa_fluctuations"]) else []
+    planes = bin(int(mask) & 15).count("1") + (len(ns) if mask & (1 << wr["dfa_fluctuations"]) else 0)
+    _window_out("window_fractal", out, planes, nch, nwin, win0)
+    if nwin:
+        sarr = (ctypes.c_int * max(len(ns), 1))(*ns)
+        _lib.check(lib.osz_window_fractal(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
+                                          int(step), int(mask), int(kmax), ctypes.cast(sarr, ctypes.c_void_p), len(ns),
+                                          ptr(out), out.stride(0), out.stride(1), int(win0), stream_ptr()))
     return nwin
 
 

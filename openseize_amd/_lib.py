@@ -61,6 +61,12 @@ WS_LDS = 4096        # OSZ_WS_LDS: ranges of up to this many bins are one tile, 
 WINDOW_CONNECTIVITY = {"cov": 0, "corr": 1, "aec": 2, "plv": 3, "ciplv": 4}
 WC_REAL = ("cov", "corr")
 WC_BLOCK = 1024      # OSZ_WC_BLOCK: a window's pair sums are chains over sub-blocks of this many samples, folded in order
+# OSZ_WR_*: a measure's bit in the mask of osz_window_fractal is 1 << its value
+WINDOW_FRACTAL = {"higuchi": 0, "katz": 1, "petrosian": 2, "dfa": 3, "dfa_fluctuations": 4}
+WR_LONGEST = 4096    # OSZ_WR_LONGEST: the longest window of osz_window_fractal (it is held in LDS)
+WR_WIDE = 512        # OSZ_WR_WIDE: windows of at least this many samples take a workgroup of 256, shorter ones a wave
+WR_KMAX = 64         # OSZ_WR_KMAX: the largest kmax of higuchi
+WR_SCALES = 32       # OSZ_WR_SCALES: the most scales of dfa
 # OSZ_SOSK_*: the kernel of a record of osz_sos_last_launches, and the record's fields in order
 SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_dual", "sos_dual_lean",
               "sos_dual2", "seal")
@@ -260,6 +266,8 @@ SIGNATURES = {
     "osz_window_pairs_work": (c_i64, [ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int]),
     "osz_window_pairs": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_int,
                                         ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "osz_window_fractal": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
+                                          c_vp, ctypes.c_int, c_vp, c_i64, c_i64, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

@@ -3,3 +3,4 @@ from openseize_amd.features.entropy import WINDOW_ENTROPIES, window_entropy  # n
 from openseize_amd.features.quantiles import WINDOW_QUANTILES, window_quantiles  # noqa: F401
 from openseize_amd.features.spectral import WINDOW_SPECTRAL, window_spectral  # noqa: F401
 from openseize_amd.features.connectivity import WINDOW_CONNECTIVITY, window_connectivity  # noqa: F401
+from openseize_amd.features.fractal import WINDOW_FRACTALS, dfa_scales, window_fractal  # noqa: F401
