@@ -1080,6 +1080,46 @@ int osz_window_fractal(const double *x, int64_t pitch, int nch, int64_t n, int64
                        int mask, int kmax, const int *scales, int nscales, double *out, int64_t plane_pitch,
                        int64_t row_pitch, int64_t win0, void *stream);
 
+/* ---- wavelet sub-band energies and statistics per window (features/wavelet.py window_wavelet) */
+/* (csrc/windowwave.hip, K21) */
+#define OSZ_WW_LONGEST 4096       /* the longest window: it and its approximations are held in LDS, 48 KB     */
+#define OSZ_WW_WIDE 512           /* windows of up to this many samples take one wave, longer ones 256 threads */
+#define OSZ_WW_TAPS 32            /* the longest filter: h and g travel in the kernel's arguments             */
+#define OSZ_WW_LEVELS 12          /* the most levels of the transform                                         */
+typedef enum {
+    OSZ_WW_ENERGY = 0,            /* E_b = sum c^2 over the band's coefficients, one plane per band        */
+    OSZ_WW_RELATIVE = 1,          /* p_b = E_b / sum_b E_b, one plane per band                             */
+    OSZ_WW_ENTROPY = 2,           /* -sum_b p_b ln p_b (/ ln B with normalize), Rosso et al. 2001          */
+    OSZ_WW_MEAN_ABS = 3,          /* mean |c| over the band's coefficients, one plane per band             */
+    OSZ_WW_STD = 4,               /* population standard deviation of the band's coefficients, per band    */
+    OSZ_WW_COUNT = 5
+} osz_window_wavelet_feature;
+/*
+ * x, the windows and mask (bit 1 << e of an osz_window_wavelet_feature) are those of
+ * osz_window_features; out[p * out_plane + c * out_pitch + k], p the plane's rank among those
+ * present in enum order, a per-band feature taking B = levels + 1 consecutive planes in the order
+ * d^1, d^2, .., d^J, a^J; nothing else of out is touched.
+ * The transform is the orthonormal discrete wavelet transform periodised within the window.  With
+ * a^0 the window of W = winsize samples (minus its mean when center is not 0, the mean from sums
+ * about the window's first sample), n_j the length of a^j, h = lo (taps values in HOST memory, taps
+ * even, 2 .. OSZ_WW_TAPS) and g_k = (-1)^k h_{taps-1-k}:
+ *   a^{j+1}_i = sum_k h_k a^j_{(2i+k) mod n_j},  d^{j+1}_i = sum_k g_k a^j_{(2i+k) mod n_j},
+ * i = 0 .. n_j / 2 - 1, j = 0 .. J - 1, J = levels (1 .. OSZ_WW_LEVELS), winsize a multiple of 2^J
+ * and 8 <= winsize <= OSZ_WW_LONGEST.  n_j < taps is allowed: the filter wraps more than once.  The
+ * sum over k runs in the order of k, fused multiply-adds.
+ *   energy    sum c^2.            relative  E_b / sum_b E_b (NaN when the sum is 0).
+ *   entropy   -sum_b p_b ln p_b, a term with p_b = 0 being 0, divided by ln B when normalize is not
+ *             0; NaN when sum_b E_b = 0.
+ *   mean_abs  (sum |c|) / count.  std  sqrt(sum (c - mean)^2 / count), the band's mean taken first.
+ * A window that holds a NaN or +-inf is NaN in every plane.  A window's bits depend on winsize, h,
+ * levels, center, normalize and its own samples only: every sum runs in an order that is a function
+ * of (winsize, levels, taps) alone and no floating-point operation is atomic.  One launch, one
+ * workgroup per (channel, window), no work space.
+ */
+int osz_window_wavelet(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step,
+                       int mask, const double *lo, int taps, int levels, int center, int normalize,
+                       double *out, int64_t out_plane, int64_t out_pitch, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

@@ -1478,7 +1478,7 @@ def bispec_finish(mode, count, k_lo, sums, power):
 
 def name_mask(table, names):
     """The bit mask a kernel takes for ``names``, keys of ``table``: one of _lib.WINDOW_FEATURE,
-    WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL, WINDOW_CONNECTIVITY and WINDOW_FRACTAL, name -> bit."""
+    WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL, WINDOW_CONNECTIVITY, WINDOW_FRACTAL and WINDOW_WAVELET, name -> bit."""
     mask = 0
     for name in names:
         mask |= 1 << table[name]
@@ -1567,6 +1567,32 @@ def window_fractal(x2d, winsize, step, mask, kmax, scales, out, win0=0):
         _lib.check(lib.osz_window_fractal(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
                                           int(step), int(mask), int(kmax), ctypes.cast(sarr, ctypes.c_void_p), len(ns),
                                           ptr(out), out.stride(0), out.stride(1), int(win0), stream_ptr()))
+    return nwin
+
+
+def window_wavelet(x2d, winsize, step, mask, lo, levels, center, normalize, out):
+    """osz_window_wavelet: the features in the bit mask ``mask`` of every window of ``winsize``
+    samples, ``step`` apart, that x2d -- (nch, n) float64 CUDA rows, unit stride along n -- holds,
+    over the ``levels`` + 1 bands of the periodised transform with the low-pass filter ``lo`` (a
+    sequence of floats), written to out[p, c, k]: out a contiguous float64 (planes, nch, room) CUDA
+    tensor whose planes are, of those asked and in the order of _lib.WINDOW_WAVELET, one per band
+    for energy, relative, mean_abs and std and one for entropy.  Returns the number of windows
+    written per row."""
+    lib = require_gpu()
+    nch, n = _window_rows("window_wavelet", x2d)
+    nwin = lib.osz_window_count(n, int(winsize), int(step))
+    if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_WAVELET):
+        raise ValueError(f"window_wavelet: bad sizes or feature mask ({n}, {winsize}, {step}, {mask})")
+    entropy = 1 << _lib.WINDOW_WAVELET["entropy"]
+    planes = bin(int(mask) & ~entropy).count("1") * (int(levels) + 1) + (1 if mask & entropy else 0)
+    _window_out("window_wavelet", out, planes, nch, nwin, 0)
+    if nwin:
+        taps = [float(v) for v in lo]
+        harr = (ctypes.c_double * max(len(taps), 1))(*taps)
+        _lib.check(lib.osz_window_wavelet(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
+                                          int(step), int(mask), ctypes.cast(harr, ctypes.c_void_p), len(taps),
+                                          int(levels), int(bool(center)), int(bool(normalize)), ptr(out),
+                                          out.stride(0), out.stride(1), stream_ptr()))
     return nwin
 
 

@@ -67,6 +67,12 @@ WR_LONGEST = 4096    # OSZ_WR_LONGEST: the longest window of osz_window_fractal 
 WR_WIDE = 512        # OSZ_WR_WIDE: windows of at least this many samples take a workgroup of 256, shorter ones a wave
 WR_KMAX = 64         # OSZ_WR_KMAX: the largest kmax of higuchi
 WR_SCALES = 32       # OSZ_WR_SCALES: the most scales of dfa
+# OSZ_WW_*: a feature's bit in the mask of osz_window_wavelet is 1 << its value
+WINDOW_WAVELET = {"energy": 0, "relative": 1, "entropy": 2, "mean_abs": 3, "std": 4}
+WW_LONGEST = 4096    # OSZ_WW_LONGEST: the longest window of osz_window_wavelet (it is held in LDS)
+WW_WIDE = 512        # OSZ_WW_WIDE: windows of up to this many samples take one wave, longer ones a workgroup of 256
+WW_TAPS = 32         # OSZ_WW_TAPS: the longest filter
+WW_LEVELS = 12       # OSZ_WW_LEVELS: the most levels of the transform
 # OSZ_SOSK_*: the kernel of a record of osz_sos_last_launches, and the record's fields in order
 SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_dual", "sos_dual_lean",
               "sos_dual2", "seal")
@@ -268,6 +274,9 @@ SIGNATURES = {
                                         ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "osz_window_fractal": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
                                           c_vp, ctypes.c_int, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "osz_window_wavelet": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, c_vp,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_i64,
+                                          c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

@@ -4,3 +4,5 @@ from openseize_amd.features.quantiles import WINDOW_QUANTILES, window_quantiles 
 from openseize_amd.features.spectral import WINDOW_SPECTRAL, window_spectral  # noqa: F401
 from openseize_amd.features.connectivity import WINDOW_CONNECTIVITY, window_connectivity  # noqa: F401
 from openseize_amd.features.fractal import WINDOW_FRACTALS, dfa_scales, window_fractal  # noqa: F401
+from openseize_amd.features.wavelet import (WAVELETS, WINDOW_WAVELET, wavelet_bands, wavelet_filters,  # noqa: F401
+                                            wavelet_level, window_wavelet)
