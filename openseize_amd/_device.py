@@ -1099,8 +1099,8 @@ def complex_join(re2d, im2d):
 
 
 def magphase(z2d, want_mag=True, want_phase=True, mag_out=None):
-    """(|z|, angle(z) in [0, 2 pi)) of a complex128 CUDA tensor (nch, n)
-    (osz_magphase); an output that is not wanted is None.  ``mag_out``: a contiguous
+    """(|z|, angle(z) in [0, 2 pi], 2 pi only for a phase that rounds to it) of a complex128
+    CUDA tensor (nch, n) (osz_magphase); an output that is not wanted is None.  ``mag_out``: a contiguous
     float64 CUDA tensor of z2d's shape that receives |z| instead of a new one."""
     lib = require_gpu()
     shape = tuple(z2d.shape)
@@ -1133,6 +1133,8 @@ def take(x2d, idx):
     lib = require_gpu()
     y = torch.empty((x2d.shape[0], idx.numel()), dtype=torch.float64,
                     device=x2d.device)
+    if idx.numel() == 0:       # an empty tensor has no address to hand over
+        return y
     _lib.check(lib.osz_take(ptr(x2d), x2d.stride(0), x2d.shape[0], ptr(idx),
                             idx.numel(), ptr(y), max(y.stride(0), 1),
                             stream_ptr()))

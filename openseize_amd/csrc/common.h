@@ -142,8 +142,10 @@ __device__ __forceinline__ void buf_store(double v, __amdgpu_buffer_rsrc_t r, un
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(buf_u2, v), r, lane_bytes, row_bytes, 2);
 }
 
-// numpy.angle(z) mapped to [0, 2 pi): the phase of osz_magphase (glue.hip), which
-// osz_phase_index (coupling.hip) recomputes to select exactly the samples whose phase passes
+// numpy.angle(z) mapped to [0, 2 pi], 2 pi only for a phase that rounds to it (a negative angle
+// below half an ulp of 2 pi, such as that of 1 - 1e-20 i; NumPy's two steps give the same): the
+// phase of osz_magphase (glue.hip), which osz_phase_index (coupling.hip) recomputes to select
+// exactly the samples whose phase passes
 __device__ __forceinline__ double phase_2pi(double2 v) {
     constexpr double kTwoPi = 6.283185307179586476925286766559;
     double p = atan2(v.y, v.x);

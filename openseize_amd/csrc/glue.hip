@@ -176,7 +176,8 @@ __global__ __launch_bounds__(256) void complex_join_kernel(const double *__restr
         z[(int64_t)c * ldz + i] = make_double2(re[(int64_t)c * ldre + i], im[(int64_t)c * ldim + i]);
 }
 
-// |z| as numpy.abs (hypot) and the phase of numpy.angle mapped to [0, 2 pi)
+// |z| as numpy.abs (hypot) and the phase of numpy.angle mapped to [0, 2 pi], 2 pi only for a
+// phase that rounds to it (phase_2pi, common.h)
 __global__ __launch_bounds__(256) void magphase_kernel(const double2 *__restrict__ z, int64_t ldz,
                                                        int64_t n, double *__restrict__ mag,
                                                        double *__restrict__ phase, int64_t ldo) {
