@@ -1120,6 +1120,51 @@ int osz_window_wavelet(const double *x, int64_t pitch, int nch, int64_t n, int64
                        int mask, const double *lo, int taps, int levels, int center, int normalize,
                        double *out, int64_t out_plane, int64_t out_pitch, void *stream);
 
+/* ---- autoregressive models per window (features/ar.py window_ar) -------------------------- */
+/* (csrc/windowar.hip, K22) */
+#define OSZ_AR_LONGEST 4096       /* the longest window: it is held on chip, in LDS and in registers          */
+#define OSZ_AR_WIDE 512           /* windows of at least this many samples take 256 threads, shorter ones 64  */
+#define OSZ_AR_ORDER 32           /* the largest model order: one lane a coefficient                          */
+typedef enum {
+    OSZ_AR_COEFFICIENTS = 0,      /* a_1 .. a_p of the order-p model, one plane each                       */
+    OSZ_AR_REFLECTION = 1,        /* k_1 .. k_p, one plane each                                            */
+    OSZ_AR_ERROR = 2,             /* E_p, the innovation variance of the order-p model                     */
+    OSZ_AR_ERROR_PATH = 3,        /* E_0 .. E_p, one plane each                                            */
+    OSZ_AR_COUNT = 4
+} osz_window_ar_measure;
+typedef enum {
+    OSZ_AR_BURG = 0,              /* Burg 1968: k_m from the forward and backward prediction errors        */
+    OSZ_AR_YULE_WALKER = 1        /* k_m from the biased autocorrelation                                   */
+} osz_window_ar_method;
+/*
+ * x, the windows, mask (bit 1 << e of an osz_window_ar_measure) and out are those of
+ * osz_window_features: out[q * plane_pitch + c * row_pitch + win0 + k], q the plane's rank among
+ * those present -- the p planes of coefficients, the p of reflection, error and then the p + 1 of
+ * error_path, p = order; nothing else of out is touched.  With x_0 .. x_{W-1} one window, W =
+ * winsize, minus its mean when center is not 0 (the mean from sums about the window's first
+ * sample), the model is x_t + sum_{k=1..p} a_k x_{t-k} = e_t (the signs of arburg):
+ *   burg         f_t = b_t = x_t, E_0 = (1 / W) sum x_t^2.  For m = 1 .. p: num = sum_{t=m}^{W-1}
+ *                f_t b_{t-1}, den = sum_{t=m}^{W-1} (f_t^2 + b_{t-1}^2) -- the direct sum, not its
+ *                downdating recursion -- k_m = -2 num / den; then for t = m .. W - 1, both from the
+ *                old values, f_t <- f_t + k_m b_{t-1} and b_t <- b_{t-1} + k_m f_t.
+ *   yule_walker  r_j = (1 / W) sum_{t=0}^{W-1-j} x_t x_{t+j}, j = 0 .. p (biased: |k| < 1), E_0 =
+ *                r_0 and k_m = -(r_m + sum_{j=1}^{m-1} a^(m-1)_j r_{m-j}) / E_{m-1}.
+ *   both         a^(m)_j = a^(m-1)_j + k_m a^(m-1)_{m-j} for j < m, a^(m)_m = k_m, E_m = E_{m-1}
+ *                (1 - k_m^2).
+ * 16 <= winsize <= OSZ_AR_LONGEST, 1 <= order <= OSZ_AR_ORDER, winsize >= 4 order; method is an
+ * osz_window_ar_method.
+ * A window that holds a NaN or +-inf is NaN in every plane.  A window with E_0 = 0 gives error and
+ * error_path 0 and coefficients and reflection NaN.  An E_{m-1} that is 0 (or a den that is 0) at a
+ * later order makes k_m and everything of the orders from m on NaN, error_path included, and moves
+ * nothing before it.  A window's bits depend on winsize, method, center and its own samples only,
+ * and those of k_m and E_m not on order: every sum runs in an order that is a function of (winsize,
+ * m) or (winsize, j) alone and no floating-point operation is atomic.  One launch, one workgroup per
+ * (channel, window), no work space.
+ */
+int osz_window_ar(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
+                  int order, int method, int center, double *out, int64_t plane_pitch, int64_t row_pitch,
+                  int64_t win0, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

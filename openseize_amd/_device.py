@@ -1480,7 +1480,8 @@ def bispec_finish(mode, count, k_lo, sums, power):
 
 def name_mask(table, names):
     """The bit mask a kernel takes for ``names``, keys of ``table``: one of _lib.WINDOW_FEATURE,
-    WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL, WINDOW_CONNECTIVITY, WINDOW_FRACTAL and WINDOW_WAVELET, name -> bit."""
+    WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL, WINDOW_CONNECTIVITY, WINDOW_FRACTAL, WINDOW_WAVELET and
+    WINDOW_AR, name -> bit."""
     mask = 0
     for name in names:
         mask |= 1 << table[name]
@@ -1595,6 +1596,29 @@ def window_wavelet(x2d, winsize, step, mask, lo, levels, center, normalize, out)
                                           int(step), int(mask), ctypes.cast(harr, ctypes.c_void_p), len(taps),
                                           int(levels), int(bool(center)), int(bool(normalize)), ptr(out),
                                           out.stride(0), out.stride(1), stream_ptr()))
+    return nwin
+
+
+def window_ar(x2d, winsize, step, mask, order, method, center, out, win0=0):
+    """osz_window_ar: the measures in the bit mask ``mask`` of the AR model of ``order`` of every
+    window of ``winsize`` samples, ``step`` apart, that x2d -- (nch, n) float64 CUDA rows, unit
+    stride along n -- holds, written to out[p, c, win0 + k]: out a contiguous float64 (planes, nch,
+    room) CUDA tensor whose planes are, of those asked and in the order of _lib.WINDOW_AR, ``order``
+    for coefficients, ``order`` for reflection, one for error and ``order`` + 1 for error_path.
+    ``method`` is a key of _lib.AR_METHOD.  Returns the number of windows written per row."""
+    lib = require_gpu()
+    nch, n = _window_rows("window_ar", x2d)
+    nwin = lib.osz_window_count(n, int(winsize), int(step))
+    if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_AR):
+        raise ValueError(f"window_ar: bad sizes or measure mask ({n}, {winsize}, {step}, {mask})")
+    p, ar = int(order), _lib.WINDOW_AR
+    planes = sum(count for name, count in (("coefficients", p), ("reflection", p), ("error", 1), ("error_path", p + 1))
+                 if mask & (1 << ar[name]))
+    _window_out("window_ar", out, planes, nch, nwin, win0)
+    if nwin:
+        _lib.check(lib.osz_window_ar(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
+                                     int(step), int(mask), p, _lib.AR_METHOD[method], int(bool(center)), ptr(out),
+                                     out.stride(0), out.stride(1), int(win0), stream_ptr()))
     return nwin
 
 

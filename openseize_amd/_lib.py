@@ -73,6 +73,12 @@ WW_LONGEST = 4096    # OSZ_WW_LONGEST: the longest window of osz_window_wavelet 
 WW_WIDE = 512        # OSZ_WW_WIDE: windows of up to this many samples take one wave, longer ones a workgroup of 256
 WW_TAPS = 32         # OSZ_WW_TAPS: the longest filter
 WW_LEVELS = 12       # OSZ_WW_LEVELS: the most levels of the transform
+# OSZ_AR_*: a measure's bit in the mask of osz_window_ar is 1 << its value
+WINDOW_AR = {"coefficients": 0, "reflection": 1, "error": 2, "error_path": 3}
+AR_METHOD = {"burg": 0, "yule_walker": 1}     # osz_window_ar_method
+AR_LONGEST = 4096    # OSZ_AR_LONGEST: the longest window of osz_window_ar (it is held on chip)
+AR_WIDE = 512        # OSZ_AR_WIDE: windows of at least this many samples take a workgroup of 256, shorter ones a wave
+AR_ORDER = 32        # OSZ_AR_ORDER: the largest model order
 # OSZ_SOSK_*: the kernel of a record of osz_sos_last_launches, and the record's fields in order
 SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_dual", "sos_dual_lean",
               "sos_dual2", "seal")
@@ -277,6 +283,8 @@ SIGNATURES = {
     "osz_window_wavelet": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, c_vp,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_i64,
                                           c_vp]),
+    "osz_window_ar": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_i64, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

@@ -6,3 +6,4 @@ from openseize_amd.features.connectivity import WINDOW_CONNECTIVITY, window_conn
 from openseize_amd.features.fractal import WINDOW_FRACTALS, dfa_scales, window_fractal  # noqa: F401
 from openseize_amd.features.wavelet import (WAVELETS, WINDOW_WAVELET, wavelet_bands, wavelet_filters,  # noqa: F401
                                             wavelet_level, window_wavelet)
+from openseize_amd.features.ar import AR_METHODS, WINDOW_ARS, window_ar  # noqa: F401
