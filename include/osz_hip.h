@@ -1165,6 +1165,53 @@ int osz_window_ar(const double *x, int64_t pitch, int nch, int64_t n, int64_t wi
                   int order, int method, int center, double *out, int64_t plane_pitch, int64_t row_pitch,
                   int64_t win0, void *stream);
 
+/* ---- lagged cross-correlation per window and pair (features/xcorr.py window_xcorr) -------- */
+/* (csrc/windowxcorr.hip, K23) */
+#define OSZ_WX_LONGEST 4096       /* the longest window                                                       */
+#define OSZ_WX_MAXLAG 64          /* the largest maxlag: the halo of the staged rows                          */
+typedef enum {
+    OSZ_WX_XCORR = 0,             /* v_ij(l) for every lag l of -maxlag .. maxlag                             */
+    OSZ_WX_PEAK = 1,              /* max over l of |v_ij(l)|                                                  */
+    OSZ_WX_LAG = 2,               /* the l that attains it (the smallest |l| of equal maxima, then l > 0)     */
+    OSZ_WX_SIGNED = 3,            /* v_ij at that lag                                                         */
+    OSZ_WX_COUNT = 4
+} osz_window_xcorr_measure;
+/*
+ * The float64 work space of one osz_window_xcorr call with these arguments, in doubles: one sum per
+ * (channel, window) and the lagged Gram products of a batch of windows, (2 maxlag + 1) nch nch
+ * doubles a window (at most 2^25 doubles, or one window's).  -1 for nch < 2 or > 16384, n < 0,
+ * winsize < 8 or > OSZ_WX_LONGEST, step < 1, maxlag < 0 or > min(OSZ_WX_MAXLAG, winsize / 2), or an
+ * empty or unknown mask.  Touches no device.
+ */
+int64_t osz_window_xcorr_work(int nch, int64_t n, int64_t winsize, int64_t step, int maxlag, int mask);
+/*
+ * x: nch float64 rows of n samples on the device, row pitch `pitch` samples.  Window k covers the
+ * samples k step .. k step + winsize - 1 of every row.  With W = winsize, L = maxlag, d_i row i
+ * minus its mean over the window and, for -L <= l <= L,
+ *   r_ij(l) = (1 / W) sum_t d_i[t] d_j[t + l],  t over max(0, -l) .. min(W, W - l) - 1,
+ * v_ij(l) is r_ij(l) / sqrt(r_ii(0) r_jj(0)) clipped to [-1, 1] (normalize = 1) or r_ij(l)
+ * (normalize = 0).  For the nwin = osz_window_count(n, winsize, step) windows, with XCORR in mask
+ *   xcorr[((k * (2 L + 1) + L + l) * nch + i) * nch + j] = v_ij(l)                          (f64)
+ * and for every other measure m of mask (an osz_window_xcorr_measure), in the order of the enum,
+ *   out[p * plane_pitch + (k * nch + i) * nch + j] = measure of rows i and j over window k  (f64)
+ * with p the measure's rank among those present, XCORR not counted.  xcorr is read only with XCORR
+ * in mask, out only with another measure; nothing else of either is touched.  v_ij(l) and v_ji(-l)
+ * are written from one value, PEAK and SIGNED to both mirrors, LAG[j, i] = -LAG[i, j].  Of equal
+ * |v| the smallest |l| wins, then the positive l (i < j).  The diagonal: lag 0, PEAK and SIGNED are
+ * 1.0 (normalize) or r_ii(0), LAG 0.0, and the lags l and -l are written from one value.  An
+ * entry's bits depend on winsize, normalize and the window's samples of rows i and j only -- not on
+ * step, k, nch, the other rows, mask, maxlag (a lag's plane) or how a stream is cut into pushes: a
+ * sum is the float64 MFMA's k-ordered chain over t = 0 .. W - 1 counted from the window's start
+ * (the factors outside the window are +0.0), about the row's mean p + s / W, p the row's first
+ * sample of the window and s the sum of x - p; nothing is atomic.  A row with a NaN or +-inf
+ * sample is NaN in its row and column in every measure; a constant row is NaN there with
+ * normalize = 1 and 0 (LAG 0) with normalize = 0.
+ * work: work_len >= osz_window_xcorr_work(...) doubles on the device, the caller's.
+ */
+int osz_window_xcorr(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int maxlag,
+                     int normalize, int mask, double *xcorr, double *out, int64_t plane_pitch, double *work,
+                     int64_t work_len, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

@@ -1480,8 +1480,8 @@ def bispec_finish(mode, count, k_lo, sums, power):
 
 def name_mask(table, names):
     """The bit mask a kernel takes for ``names``, keys of ``table``: one of _lib.WINDOW_FEATURE,
-    WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL, WINDOW_CONNECTIVITY, WINDOW_FRACTAL, WINDOW_WAVELET and
-    WINDOW_AR, name -> bit."""
+    WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL, WINDOW_CONNECTIVITY, WINDOW_FRACTAL, WINDOW_WAVELET,
+    WINDOW_AR and WINDOW_XCORR, name -> bit."""
     mask = 0
     for name in names:
         mask |= 1 << table[name]
@@ -1715,4 +1715,37 @@ def window_pairs(x2d, winsize, step, ddof, mask, out):
         work = torch.empty(max(need, 1), dtype=torch.float64, device=x2d.device)
         _lib.check(lib.osz_window_pairs(ptr(x2d), max(x2d.stride(0), n), nch, n, int(cplx), int(winsize), int(step),
                                         int(ddof), int(mask), ptr(out), out.stride(0), ptr(work), need, stream_ptr()))
+    return nwin
+
+
+def window_xcorr(x2d, winsize, step, maxlag, normalize, mask, xcorr, out):
+    """osz_window_xcorr: the measures in the bit mask ``mask`` (_lib.WINDOW_XCORR) of every window of
+    ``winsize`` samples, ``step`` apart, that x2d -- (nch, n) float64 CUDA rows, unit stride along n --
+    holds, over the lags -``maxlag`` .. ``maxlag``.  ``xcorr``: a contiguous float64 (nwin, 2 maxlag + 1,
+    nch, nch) CUDA tensor, written as xcorr[k, maxlag + l, i, j] with the xcorr bit set, else None.
+    ``out``: a contiguous float64 (planes, nwin, nch, nch) CUDA tensor, one plane per measure of peak,
+    lag and signed present, in that order, else None.  The work space is allocated here and freed on
+    return.  Returns the number of windows written."""
+    lib = require_gpu()
+    nch, n = _window_rows("window_xcorr", x2d)
+    need = lib.osz_window_xcorr_work(nch, n, int(winsize), int(step), int(maxlag), int(mask))
+    if need < 0 or not isinstance(normalize, bool):
+        raise ValueError(f"window_xcorr: bad sizes or measures ({nch}, {n}, {winsize}, {step}, {maxlag}, "
+                         f"{normalize!r}, {mask})")
+    nwin = lib.osz_window_count(n, int(winsize), int(step))
+    lags = 2 * int(maxlag) + 1
+    planes = bin(int(mask) >> 1).count("1")
+    want = ((xcorr, (nwin, lags, nch, nch), mask & 1), (out, (planes, nwin, nch, nch), planes))
+    for arr, shape, asked in want:
+        if (arr is None) != (not asked) or (asked and (arr.dtype != torch.float64 or tuple(arr.shape) != shape
+                                                       or not arr.is_contiguous() or arr.device != x2d.device)):
+            raise ValueError(f"window_xcorr: mask {mask} takes xcorr and out contiguous float64 "
+                             f"{[s if a else None for _, s, a in want]}, got "
+                             f"{[None if a is None else tuple(a.shape) for a, _, _ in want]}")
+    if nwin:
+        work = torch.empty(max(need, 1), dtype=torch.float64, device=x2d.device)
+        _lib.check(lib.osz_window_xcorr(ptr(x2d), max(x2d.stride(0), n), nch, n, int(winsize), int(step), int(maxlag),
+                                        int(normalize), int(mask), ptr(xcorr) if mask & 1 else None,
+                                        ptr(out) if planes else None, out.stride(0) if planes else 0, ptr(work), need,
+                                        stream_ptr()))
     return nwin

@@ -79,6 +79,10 @@ AR_METHOD = {"burg": 0, "yule_walker": 1}     # osz_window_ar_method
 AR_LONGEST = 4096    # OSZ_AR_LONGEST: the longest window of osz_window_ar (it is held on chip)
 AR_WIDE = 512        # OSZ_AR_WIDE: windows of at least this many samples take a workgroup of 256, shorter ones a wave
 AR_ORDER = 32        # OSZ_AR_ORDER: the largest model order
+# OSZ_WX_*: a measure's bit in the mask of osz_window_xcorr is 1 << its value
+WINDOW_XCORR = {"xcorr": 0, "peak": 1, "lag": 2, "signed": 3}
+WX_LONGEST = 4096    # OSZ_WX_LONGEST: the longest window of osz_window_xcorr
+WX_MAXLAG = 64       # OSZ_WX_MAXLAG: the largest maxlag (the halo of the rows staged on chip)
 # OSZ_SOSK_*: the kernel of a record of osz_sos_last_launches, and the record's fields in order
 SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_dual", "sos_dual_lean",
               "sos_dual2", "seal")
@@ -285,6 +289,9 @@ SIGNATURES = {
                                           c_vp]),
     "osz_window_ar": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "osz_window_xcorr_work": (c_i64, [ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int]),
+    "osz_window_xcorr": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

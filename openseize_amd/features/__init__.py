@@ -7,3 +7,4 @@ from openseize_amd.features.fractal import WINDOW_FRACTALS, dfa_scales, window_f
 from openseize_amd.features.wavelet import (WAVELETS, WINDOW_WAVELET, wavelet_bands, wavelet_filters,  # noqa: F401
                                             wavelet_level, window_wavelet)
 from openseize_amd.features.ar import AR_METHODS, WINDOW_ARS, window_ar  # noqa: F401
+from openseize_amd.features.xcorr import WINDOW_XCORR, window_xcorr, xcorr_lags  # noqa: F401
