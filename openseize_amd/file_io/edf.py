@@ -223,12 +223,20 @@ class Reader:
         reclen = sum(hdr.samples_per_record)
         offset = hdr.header_bytes + a * reclen * 2
         self._fobj.seek(0)
-        return np.fromfile(self._fobj, "<i2", cnt * reclen, offset=offset)
+        raw = np.fromfile(self._fobj, "<i2", cnt * reclen, offset=offset)
+        if raw.size != cnt * reclen:
+            # a file shorter than its header says (an interrupted recording): the decode would
+            # index past the end of what was read; the reference's reshape raises here too
+            raise ValueError(
+                "{}: records [{}, {}) hold {} samples according to the header, the file has {} "
+                "of them".format(self.path, a, a + cnt, cnt * reclen, raw.size))
+        return raw
 
     def read(self, start, stop=None, padvalue=np.nan, device=False):
         """Samples [start, stop) of this reader's channels as a float64
         (channels, samples) array (edf.py:558-586); ``device=True`` returns a
-        CUDA tensor instead of an ndarray."""
+        CUDA tensor instead of an ndarray.  ValueError, before the device is
+        touched, when the file ends before the records the read needs."""
         import torch
         nchan = len(self.channels)
         if start > max(self.header.samples):
@@ -239,11 +247,13 @@ class Reader:
         start, stop = int(start), int(stop)
         self.open()
         p = self.plan(start, stop, self.channels)
+        records = self._records(p["rec0"], p["nrec"])      # raises on a truncated file
         lib = dev.require_gpu()
+        if p["width"] == 0:        # nothing to decode, and an empty tensor has no address
+            out = torch.empty((nchan, 0), dtype=torch.float64, device="cuda")
+            return out if device else out.cpu().numpy()
         idx = [self.header.channels.index(c) for c in self.channels]
-        raw = torch.from_numpy(self._records(p["rec0"], p["nrec"])).cuda()
-        if raw.numel() == 0:
-            raw = torch.zeros(1, dtype=torch.int16, device="cuda")
+        raw = torch.from_numpy(records).cuda()
         t = lambda arr: torch.from_numpy(np.ascontiguousarray(arr)).cuda()
         choff, spr, lens = t(p["choff"]), t(p["spr"]), t(p["len"])
         slope, offset = t(self.header.slopes[idx]), t(self.header.offsets[idx])

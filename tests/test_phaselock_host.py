@@ -29,16 +29,19 @@ def split(flat, lengths):
     return np.split(flat, np.cumsum(lengths)[:-1])
 
 
-def lock_sums(amps, indices, shifts, max_shift, W):
+def lock_sums(amps, indices, shifts, max_shift, W, dtype=np.float64):
     """Restatement of osz_lock_accumulate over all chunks: (sums (S+1, W), counts (S+1,)).
     Set 0 is ``indices``; set s is (indices + shifts[s-1]) % max_shift.  With h = ceil(W/2)
     a position q of a chunk of length L contributes amps[q - h : q - h + W]**2 iff
-    h <= q and q + W // 2 <= L -- the windows the reference's slicing leaves whole."""
+    h <= q and q + W // 2 <= L -- the windows the reference's slicing leaves whole.
+    ``dtype``: the format the squares are taken and summed in (np.longdouble for a reference
+    whose own error is negligible)."""
     h = -(-W // 2)
-    sums = np.zeros((len(shifts) + 1, W))
+    sums = np.zeros((len(shifts) + 1, W), dtype=dtype)
     counts = np.zeros(len(shifts) + 1, dtype=np.int64)
     for s, shift in enumerate([None] + list(shifts)):
         for amp, idx in zip(amps, indices):
+            amp = np.asarray(amp, dtype=dtype)
             q = np.asarray(idx, dtype=np.int64)
             q = q if shift is None else (q + shift) % max_shift
             q = q[(q >= h) & (q + W // 2 <= amp.size)]
