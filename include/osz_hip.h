@@ -1212,6 +1212,50 @@ int osz_window_xcorr(const double *x, int64_t pitch, int nch, int64_t n, int64_t
                      int normalize, int mask, double *xcorr, double *out, int64_t plane_pitch, double *work,
                      int64_t work_len, void *stream);
 
+/* ---- pairwise Granger causality per window (features/granger.py window_granger) --------- */
+/* (csrc/windowgranger.hip, K24) */
+#define OSZ_WG_LONGEST 4096       /* the longest window                                                       */
+#define OSZ_WG_MAXORDER 16        /* the largest model order: the coefficient blocks of a pair fill the LDS   */
+typedef enum {
+    OSZ_WG_GRANGER = 0,           /* F_{i->j} = ln(E_j / S_jj): row the source, column the target            */
+    OSZ_WG_INSTANT = 1,           /* ln(S_ii S_jj / det S)                                                    */
+    OSZ_WG_TOTAL = 2,             /* (F_{i->j} + F_{j->i}) + instant                                          */
+    OSZ_WG_COUNT = 3
+} osz_window_granger_measure;
+/*
+ * The float64 work space of one osz_window_granger call with these arguments, in doubles: a sum and
+ * a restricted model's error per (channel, window) and the lagged Gram products of a batch of
+ * windows, (2 order + 1) nch nch doubles a window (at most 2^25 doubles, or one window's).  -1 for
+ * nch < 2 or > 16384, n < 0, winsize < 16 or > OSZ_WG_LONGEST, step < 1, order < 1 or >
+ * min(OSZ_WG_MAXORDER, winsize / 8), or an empty or unknown mask.  Touches no device.
+ */
+int64_t osz_window_granger_work(int nch, int64_t n, int64_t winsize, int64_t step, int order, int mask);
+/*
+ * x and the windows are those of osz_window_xcorr.  With W = winsize, p = order, d_i row i minus its
+ * mean over the window, r_ab(l) = (1 / W) sum_t d_a[t] d_b[t + l] as there and z_t = (d_i[t],
+ * d_j[t])^T for the ordered pair (i, j):
+ *   C(l) = E[z_t z_{t-l}^T], C(l)_ab = r_ba(l), C(-l) = C(l)^T;
+ *   A_1 .. A_p solve C(l) = sum_{k=1..p} A_k C(l - k), l = 1 .. p (the bivariate Yule-Walker
+ *   equations, by the block Levinson recursion);  S = C(0) - sum_k A_k C(k)^T;
+ *   E_i, E_j: the errors of the scalar Yule-Walker models of order p of d_i and d_j alone;
+ *   GRANGER[i, j] = ln(E_j / S_jj),  INSTANT[i, j] = ln(S_ii S_jj / det S),
+ *   TOTAL[i, j] = (GRANGER[i, j] + GRANGER[j, i]) + INSTANT[i, j].
+ * For the nwin = osz_window_count(n, winsize, step) windows and every measure m of mask (bit 1 << m),
+ * in the order of the enum,
+ *   out[q * plane_pitch + (k * nch + i) * nch + j] = measure of rows i and j over window k  (f64)
+ * with q the measure's rank among those present; nothing else of out is touched.  A finite value
+ * below 0 is written as +0.0.  INSTANT and TOTAL are written to both mirrors from one value.  The
+ * diagonal is 0.0, and NaN where E_i is not finite and > 0.  A pair is NaN in every measure and both
+ * directions when one of E_i, E_j, S_ii, S_jj, det S is not finite and > 0: a row with a NaN or
+ * +-inf sample, or a constant row, is NaN in its row and column.  An entry's bits depend on winsize,
+ * order and the window's samples of rows i and j only -- not on step, k, nch, the other rows, mask
+ * or how a stream is cut into pushes: the sums are osz_window_xcorr's, the order of every operation
+ * after them is a function of p alone, and nothing is atomic.
+ * work: work_len >= osz_window_granger_work(...) doubles on the device, the caller's.
+ */
+int osz_window_granger(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int order,
+                       int mask, double *out, int64_t plane_pitch, double *work, int64_t work_len, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

@@ -1481,7 +1481,7 @@ def bispec_finish(mode, count, k_lo, sums, power):
 def name_mask(table, names):
     """The bit mask a kernel takes for ``names``, keys of ``table``: one of _lib.WINDOW_FEATURE,
     WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL, WINDOW_CONNECTIVITY, WINDOW_FRACTAL, WINDOW_WAVELET,
-    WINDOW_AR and WINDOW_XCORR, name -> bit."""
+    WINDOW_AR, WINDOW_XCORR and WINDOW_GRANGER, name -> bit."""
     mask = 0
     for name in names:
         mask |= 1 << table[name]
@@ -1748,4 +1748,29 @@ def window_xcorr(x2d, winsize, step, maxlag, normalize, mask, xcorr, out):
                                         int(normalize), int(mask), ptr(xcorr) if mask & 1 else None,
                                         ptr(out) if planes else None, out.stride(0) if planes else 0, ptr(work), need,
                                         stream_ptr()))
+    return nwin
+
+
+def window_granger(x2d, winsize, step, order, mask, out):
+    """osz_window_granger: the measures in the bit mask ``mask`` (_lib.WINDOW_GRANGER) of every window
+    of ``winsize`` samples, ``step`` apart, that x2d -- (nch, n) float64 CUDA rows, unit stride along
+    n -- holds, from bivariate and scalar Yule-Walker models of order ``order``, written to
+    out[p, k, i, j] (row the source, column the target): out a contiguous float64 (planes, nwin, nch,
+    nch) CUDA tensor, one plane per measure present in the order of _lib.WINDOW_GRANGER.  The work
+    space is allocated here and freed on return.  Returns the number of windows written."""
+    lib = require_gpu()
+    nch, n = _window_rows("window_granger", x2d)
+    need = lib.osz_window_granger_work(nch, n, int(winsize), int(step), int(order), int(mask))
+    if need < 0:
+        raise ValueError(f"window_granger: bad sizes or measures ({nch}, {n}, {winsize}, {step}, {order}, {mask})")
+    nwin = lib.osz_window_count(n, int(winsize), int(step))
+    planes = bin(int(mask)).count("1")
+    if (out.dtype != torch.float64 or tuple(out.shape) != (planes, nwin, nch, nch) or not out.is_contiguous()
+            or out.device != x2d.device):
+        raise ValueError(f"window_granger: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nwin}, {nch}, "
+                         f"{nch}) on the device of the data")
+    if nwin:
+        work = torch.empty(max(need, 1), dtype=torch.float64, device=x2d.device)
+        _lib.check(lib.osz_window_granger(ptr(x2d), max(x2d.stride(0), n), nch, n, int(winsize), int(step), int(order),
+                                          int(mask), ptr(out), out.stride(0), ptr(work), need, stream_ptr()))
     return nwin

@@ -83,6 +83,10 @@ AR_ORDER = 32        # OSZ_AR_ORDER: the largest model order
 WINDOW_XCORR = {"xcorr": 0, "peak": 1, "lag": 2, "signed": 3}
 WX_LONGEST = 4096    # OSZ_WX_LONGEST: the longest window of osz_window_xcorr
 WX_MAXLAG = 64       # OSZ_WX_MAXLAG: the largest maxlag (the halo of the rows staged on chip)
+# OSZ_WG_*: a measure's bit in the mask of osz_window_granger is 1 << its value
+WINDOW_GRANGER = {"granger": 0, "instant": 1, "total": 2}
+WG_LONGEST = 4096    # OSZ_WG_LONGEST: the longest window of osz_window_granger
+WG_MAXORDER = 16     # OSZ_WG_MAXORDER: the largest model order (a pair's coefficient blocks are held in LDS)
 # OSZ_SOSK_*: the kernel of a record of osz_sos_last_launches, and the record's fields in order
 SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_dual", "sos_dual_lean",
               "sos_dual2", "seal")
@@ -292,6 +296,9 @@ SIGNATURES = {
     "osz_window_xcorr_work": (c_i64, [ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int]),
     "osz_window_xcorr": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "osz_window_granger_work": (c_i64, [ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int]),
+    "osz_window_granger": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
+                                          c_vp, c_i64, c_vp, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

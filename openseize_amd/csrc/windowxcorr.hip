@@ -15,6 +15,7 @@
 // (a factor outside the window is a staged +0.0), whichever lags share its workgroup; a row's sum
 // is lane-strided and folded by wave_sum63.
 #include "pair_tile.h"
+#include "windowxcorr.h"
 
 namespace osz {
 
@@ -250,6 +251,28 @@ xcorr_finish_kernel(const double *__restrict__ part, int nch, int ntile, int L, 
     }
 }
 
+// The windows whose G, `one` doubles a window, one batch holds: kWxGramCap doubles, a grid's y.
+int64_t wx_batch(int64_t one) {
+    const int64_t batch = kWxGramCap / one;
+    return batch < 1 ? 1 : batch > 65535 ? 65535 : batch;
+}
+
+int wx_lagged_gram(const double *x, int64_t pitch, int nch, int64_t W, int64_t step, int L, int64_t w0,
+                   int64_t count, double *chan, double *part, const char *timer, hipStream_t st) {
+    OSZ_REQUIRE(count >= 1 && count <= 65535 && L >= 0 && L <= OSZ_WX_MAXLAG && L <= W / 2 && nch >= 1 &&
+                    nch <= 16384 && W <= OSZ_WX_LONGEST,
+                "wx_lagged_gram: bad sizes");
+    const int nblk = (nch + kWxSide - 1) / kWxSide, ngroups = (2 * L + 1 + kWxGroup - 1) / kWxGroup;
+    hipLaunchKernelGGL(xcorr_sums_kernel, dim3((unsigned)count, (unsigned)nch), dim3(kWave), 0, st, x + w0 * step,
+                       pitch, nch, W, step, chan + w0 * nch);
+    OSZ_HIP(hipGetLastError());
+    KernelTimer t(timer, st);
+    hipLaunchKernelGGL(xcorr_gram_kernel, dim3((unsigned)(nblk * (nblk + 1) / 2), (unsigned)count, (unsigned)ngroups),
+                       dim3(kWxThreads), 0, st, x, pitch, nch, (int)W, step, w0, nblk, L, chan, part);
+    OSZ_HIP(hipGetLastError());
+    return OSZ_OK;
+}
+
 struct WxPlan {
     int64_t nwin, chan, one, batch, gram;                    // counts of doubles but nwin and batch
 };
@@ -262,8 +285,7 @@ static bool wx_plan(int nch, int64_t n, int64_t W, int64_t step, int L, int mask
     p->nwin = n < W ? 0 : (n - W) / step + 1;
     p->chan = (int64_t)nch * p->nwin;
     p->one = (int64_t)(2 * L + 1) * nch * nch;
-    int64_t batch = kWxGramCap / p->one;
-    batch = batch < 1 ? 1 : batch > 65535 ? 65535 : batch;
+    const int64_t batch = wx_batch(p->one);
     p->batch = batch < p->nwin ? batch : p->nwin;
     p->gram = p->batch * p->one;
     return true;
