@@ -1508,23 +1508,30 @@ def _window_out(who, out, planes, nch, nwin, win0):
                          f">= {win0 + nwin})")
 
 
+def _window_open(who, x2d, winsize, step, mask, table, noun):
+    """``(lib, nch, n, nwin, pitch)`` for ``who``, a per-channel window wrapper: the library, the
+    shape of the rows ``x2d``, the windows a row holds and the pitch of the rows as the kernel takes
+    it; ``who``'s ValueError for rows of another kind, bad sizes or a ``mask`` that is not one of
+    ``table``'s (``noun``: what ``who`` calls the bits, "feature" or "measure")."""
+    lib = require_gpu()
+    nch, n = _window_rows(who, x2d)
+    nwin = lib.osz_window_count(n, int(winsize), int(step))
+    if nwin < 0 or mask < 1 or mask >= 1 << len(table):
+        raise ValueError(f"{who}: bad sizes or {noun} mask ({n}, {winsize}, {step}, {mask})")
+    return lib, nch, n, nwin, max(x2d.stride(0), n) if nch > 1 else n
+
+
 def window_features(x2d, winsize, step, mask, out, win0=0):
     """osz_window_features: the features in the bit mask ``mask`` of every window of ``winsize``
     samples, ``step`` apart, that x2d -- (nch, n) float64 CUDA rows, unit stride along n -- holds,
     written to out[p, c, win0 + k]: out a contiguous float64 (planes, nch, room) CUDA tensor, one
     plane per feature present in the order of _lib.WINDOW_FEATURE.  Returns the number of windows
     written per row."""
-    lib = require_gpu()
-    nch, n = _window_rows("window_features", x2d)
-    planes = bin(int(mask)).count("1")
-    nwin = lib.osz_window_count(n, int(winsize), int(step))
-    if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_FEATURE):
-        raise ValueError(f"window_features: bad sizes or feature mask ({n}, {winsize}, {step}, {mask})")
-    _window_out("window_features", out, planes, nch, nwin, win0)
+    lib, nch, n, nwin, pitch = _window_open("window_features", x2d, winsize, step, mask, _lib.WINDOW_FEATURE, "feature")
+    _window_out("window_features", out, bin(int(mask)).count("1"), nch, nwin, win0)
     if nwin:
-        _lib.check(lib.osz_window_features(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
-                                           int(step), int(mask), ptr(out), out.stride(0), out.stride(1), int(win0),
-                                           stream_ptr()))
+        _lib.check(lib.osz_window_features(ptr(x2d), pitch, nch, n, int(winsize), int(step), int(mask), ptr(out),
+                                           out.stride(0), out.stride(1), int(win0), stream_ptr()))
     return nwin
 
 
@@ -1534,18 +1541,12 @@ def window_entropy(x2d, winsize, step, mask, m, r, tolerance, order, delay, norm
     written to out[p, c, win0 + k]: out a contiguous float64 (planes, nch, room) CUDA tensor, one
     plane per measure present in the order of _lib.WINDOW_ENTROPY.  ``tolerance`` is a key of
     _lib.WE_TOLERANCE.  Returns the number of windows written per row."""
-    lib = require_gpu()
-    nch, n = _window_rows("window_entropy", x2d)
-    planes = bin(int(mask)).count("1")
-    nwin = lib.osz_window_count(n, int(winsize), int(step))
-    if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_ENTROPY):
-        raise ValueError(f"window_entropy: bad sizes or measure mask ({n}, {winsize}, {step}, {mask})")
-    _window_out("window_entropy", out, planes, nch, nwin, win0)
+    lib, nch, n, nwin, pitch = _window_open("window_entropy", x2d, winsize, step, mask, _lib.WINDOW_ENTROPY, "measure")
+    _window_out("window_entropy", out, bin(int(mask)).count("1"), nch, nwin, win0)
     if nwin:
-        _lib.check(lib.osz_window_entropy(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
-                                          int(step), int(mask), int(m), float(r), _lib.WE_TOLERANCE[tolerance],
-                                          int(order), int(delay), int(bool(normalize)), ptr(out), out.stride(0),
-                                          out.stride(1), int(win0), stream_ptr()))
+        _lib.check(lib.osz_window_entropy(ptr(x2d), pitch, nch, n, int(winsize), int(step), int(mask), int(m), float(r),
+                                          _lib.WE_TOLERANCE[tolerance], int(order), int(delay), int(bool(normalize)),
+                                          ptr(out), out.stride(0), out.stride(1), int(win0), stream_ptr()))
     return nwin
 
 
@@ -1556,20 +1557,16 @@ def window_fractal(x2d, winsize, step, mask, kmax, scales, out, win0=0):
     planes are, of those asked and in the order of _lib.WINDOW_FRACTAL, higuchi, katz, petrosian,
     dfa and one per value of ``scales`` for dfa_fluctuations (a sequence of ints, read only with a
     dfa bit set).  Returns the number of windows written per row."""
-    lib = require_gpu()
-    nch, n = _window_rows("window_fractal", x2d)
-    nwin = lib.osz_window_count(n, int(winsize), int(step))
-    if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_FRACTAL):
-        raise ValueError(f"window_fractal: bad sizes or measure mask ({n}, {winsize}, {step}, {mask})")
     wr = _lib.WINDOW_FRACTAL
+    lib, nch, n, nwin, pitch = _window_open("window_fractal", x2d, winsize, step, mask, wr, "measure")
     ns = [int(s) for s in scales] if mask & (1 << wr["dfa"] | 1 << wr["dfa_fluctuations"]) else []
     planes = bin(int(mask) & 15).count("1") + (len(ns) if mask & (1 << wr["dfa_fluctuations"]) else 0)
     _window_out("window_fractal", out, planes, nch, nwin, win0)
     if nwin:
         sarr = (ctypes.c_int * max(len(ns), 1))(*ns)
-        _lib.check(lib.osz_window_fractal(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
-                                          int(step), int(mask), int(kmax), ctypes.cast(sarr, ctypes.c_void_p), len(ns),
-                                          ptr(out), out.stride(0), out.stride(1), int(win0), stream_ptr()))
+        _lib.check(lib.osz_window_fractal(ptr(x2d), pitch, nch, n, int(winsize), int(step), int(mask), int(kmax),
+                                          ctypes.cast(sarr, ctypes.c_void_p), len(ns), ptr(out), out.stride(0),
+                                          out.stride(1), int(win0), stream_ptr()))
     return nwin
 
 
@@ -1581,21 +1578,16 @@ def window_wavelet(x2d, winsize, step, mask, lo, levels, center, normalize, out)
     tensor whose planes are, of those asked and in the order of _lib.WINDOW_WAVELET, one per band
     for energy, relative, mean_abs and std and one for entropy.  Returns the number of windows
     written per row."""
-    lib = require_gpu()
-    nch, n = _window_rows("window_wavelet", x2d)
-    nwin = lib.osz_window_count(n, int(winsize), int(step))
-    if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_WAVELET):
-        raise ValueError(f"window_wavelet: bad sizes or feature mask ({n}, {winsize}, {step}, {mask})")
+    lib, nch, n, nwin, pitch = _window_open("window_wavelet", x2d, winsize, step, mask, _lib.WINDOW_WAVELET, "feature")
     entropy = 1 << _lib.WINDOW_WAVELET["entropy"]
     planes = bin(int(mask) & ~entropy).count("1") * (int(levels) + 1) + (1 if mask & entropy else 0)
     _window_out("window_wavelet", out, planes, nch, nwin, 0)
     if nwin:
         taps = [float(v) for v in lo]
         harr = (ctypes.c_double * max(len(taps), 1))(*taps)
-        _lib.check(lib.osz_window_wavelet(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
-                                          int(step), int(mask), ctypes.cast(harr, ctypes.c_void_p), len(taps),
-                                          int(levels), int(bool(center)), int(bool(normalize)), ptr(out),
-                                          out.stride(0), out.stride(1), stream_ptr()))
+        _lib.check(lib.osz_window_wavelet(ptr(x2d), pitch, nch, n, int(winsize), int(step), int(mask),
+                                          ctypes.cast(harr, ctypes.c_void_p), len(taps), int(levels), int(bool(center)),
+                                          int(bool(normalize)), ptr(out), out.stride(0), out.stride(1), stream_ptr()))
     return nwin
 
 
@@ -1606,19 +1598,15 @@ def window_ar(x2d, winsize, step, mask, order, method, center, out, win0=0):
     room) CUDA tensor whose planes are, of those asked and in the order of _lib.WINDOW_AR, ``order``
     for coefficients, ``order`` for reflection, one for error and ``order`` + 1 for error_path.
     ``method`` is a key of _lib.AR_METHOD.  Returns the number of windows written per row."""
-    lib = require_gpu()
-    nch, n = _window_rows("window_ar", x2d)
-    nwin = lib.osz_window_count(n, int(winsize), int(step))
-    if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_AR):
-        raise ValueError(f"window_ar: bad sizes or measure mask ({n}, {winsize}, {step}, {mask})")
     p, ar = int(order), _lib.WINDOW_AR
+    lib, nch, n, nwin, pitch = _window_open("window_ar", x2d, winsize, step, mask, ar, "measure")
     planes = sum(count for name, count in (("coefficients", p), ("reflection", p), ("error", 1), ("error_path", p + 1))
                  if mask & (1 << ar[name]))
     _window_out("window_ar", out, planes, nch, nwin, win0)
     if nwin:
-        _lib.check(lib.osz_window_ar(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
-                                     int(step), int(mask), p, _lib.AR_METHOD[method], int(bool(center)), ptr(out),
-                                     out.stride(0), out.stride(1), int(win0), stream_ptr()))
+        _lib.check(lib.osz_window_ar(ptr(x2d), pitch, nch, n, int(winsize), int(step), int(mask), p,
+                                     _lib.AR_METHOD[method], int(bool(center)), ptr(out), out.stride(0), out.stride(1),
+                                     int(win0), stream_ptr()))
     return nwin
 
 
@@ -1628,19 +1616,16 @@ def window_quantiles(x2d, winsize, step, mask, q, out, win0=0):
     written to out[p, c, win0 + k]: out a contiguous float64 (planes, nch, room) CUDA tensor whose
     planes are, of those asked, median, mad and one per value of ``q`` (a sequence of floats, read
     only with the quantile bit set).  Returns the number of windows written per row."""
-    lib = require_gpu()
-    nch, n = _window_rows("window_quantiles", x2d)
-    nwin = lib.osz_window_count(n, int(winsize), int(step))
-    if nwin < 0 or mask < 1 or mask >= 1 << len(_lib.WINDOW_QUANTILE):
-        raise ValueError(f"window_quantiles: bad sizes or measure mask ({n}, {winsize}, {step}, {mask})")
+    lib, nch, n, nwin, pitch = _window_open("window_quantiles", x2d, winsize, step, mask, _lib.WINDOW_QUANTILE,
+                                            "measure")
     qs = [float(p) for p in q] if mask & (1 << _lib.WINDOW_QUANTILE["quantile"]) else []
     planes = bin(int(mask) & 3).count("1") + len(qs)
     _window_out("window_quantiles", out, planes, nch, nwin, win0)
     if nwin:
         qarr = (ctypes.c_double * max(len(qs), 1))(*qs)
-        _lib.check(lib.osz_window_quantiles(ptr(x2d), max(x2d.stride(0), n) if nch > 1 else n, nch, n, int(winsize),
-                                            int(step), int(mask), ctypes.cast(qarr, ctypes.c_void_p), len(qs),
-                                            ptr(out), out.stride(0), out.stride(1), int(win0), stream_ptr()))
+        _lib.check(lib.osz_window_quantiles(ptr(x2d), pitch, nch, n, int(winsize), int(step), int(mask),
+                                            ctypes.cast(qarr, ctypes.c_void_p), len(qs), ptr(out), out.stride(0),
+                                            out.stride(1), int(win0), stream_ptr()))
     return nwin
 
 

@@ -89,6 +89,40 @@ __device__ __forceinline__ double wave_sum63(double v) {
     return v;
 }
 
+// Maximum over the 64 lanes of values >= 0, valid in lane 63: wave_sum63 with max (a lane
+// without a source reads 0).
+__device__ __forceinline__ double wave_max63(double v) {
+    v = __builtin_fmax(v, dpp_mov0<0x111>(v));
+    v = __builtin_fmax(v, dpp_mov0<0x112>(v));
+    v = __builtin_fmax(v, dpp_mov0<0x114>(v));
+    v = __builtin_fmax(v, dpp_mov0<0x118>(v));
+    v = __builtin_fmax(v, dpp_mov0<0x142>(v));
+    v = __builtin_fmax(v, dpp_mov0<0x143>(v));
+    return v;
+}
+
+// lane L's v in every lane (L a constant: two v_readlane, the value arrives in scalar registers)
+template <int L>
+__device__ __forceinline__ double lane_of(double v) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), L);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), L);
+    return __hiloint2double(hi, lo);
+}
+
+// lane 63's v -- where wave_sum63 and wave_max63 leave their result -- in every lane
+__device__ __forceinline__ double lane63(double v) { return lane_of<kWave - 1>(v); }
+
+// the v of lane `lane` (0 .. 63, each lane's own choice: two ds_bpermute)
+__device__ __forceinline__ double lane_from(double v, int lane) {
+    const int lo = __builtin_amdgcn_ds_bpermute(lane << 2, __double2loint(v));
+    const int hi = __builtin_amdgcn_ds_bpermute(lane << 2, __double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+
+// Where element t of an array lies in LDS with one double of padding every 32: threads that each
+// walk their own run of a power-of-two length then read at an odd stride, free of bank conflicts.
+__device__ __forceinline__ int lds_pad32(int t) { return t + (t >> 5); }
+
 // wave-private LDS hand-offs need no workgroup barrier: LDS executes one
 // wave's instructions in order; this only stops the compiler reordering them
 __device__ __forceinline__ void wave_lds_fence() {

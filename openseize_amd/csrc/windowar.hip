@@ -36,7 +36,7 @@
 // operation is atomic.
 #include <cmath>
 
-#include "common.h"
+#include "window_block.h"
 
 namespace osz {
 
@@ -46,38 +46,12 @@ constexpr int kArLags = OSZ_AR_ORDER + 1;
 static_assert(OSZ_AR_WIDE <= 8 * kWave && OSZ_AR_LONGEST <= 16 * 256, "window_ar_kernel: samples a thread");
 static_assert(kArLags <= kWave, "window_ar_kernel: one lane a coefficient");
 
-struct WaArgs {
-    const double *x;      // (nch, n) rows, row pitch `pitch`
-    int64_t pitch, step;
-    int64_t nwin;         // windows of this launch (per channel)
-    int W, mask;
+struct WaArgs : WinHead {
     int order, method, center;
-    double *out;          // already at the first window of this launch
-    int64_t plane_pitch, row_pitch;
 };
-
-// lane 63's v in every lane
-__device__ __forceinline__ double wa_lane63(double v) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), kWave - 1);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), kWave - 1);
-    return __hiloint2double(hi, lo);
-}
-
-// the v of lane `from` (0 .. 63, a lane's own choice)
-__device__ __forceinline__ double wa_lane_of(double v, int from) {
-    const int lo = __builtin_amdgcn_ds_bpermute(from << 2, __double2loint(v));
-    const int hi = __builtin_amdgcn_ds_bpermute(from << 2, __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
 
 // the v of the lane below (wave_shr:1); 0 in lane 0
 __device__ __forceinline__ double wa_below(double v) { return dpp_mov0<0x138>(v); }
-
-// where sample t lies in LDS: burg pads one double every 32
-template <bool PAD>
-__device__ __forceinline__ int wa_at(int t) {
-    return PAD ? t + (t >> 5) : t;
-}
 
 // The reflection coefficients of Burg's recursion, k_m into kk[m], m = 1 .. p.  The window is in
 // `win`, padded, zeros from W to NT R + 1.
@@ -89,8 +63,8 @@ __device__ __forceinline__ void wa_burg(const double *win, int W, int p, int tid
     double f[R], b[R];
 #pragma unroll
     for (int i = 0; i < R; ++i) {
-        b[i] = win[wa_at<true>(base + i)];
-        f[i] = win[wa_at<true>(base + i + 1)];
+        b[i] = win[lds_pad32(base + i)];
+        f[i] = win[lds_pad32(base + i + 1)];
     }
     for (int m = 1; m <= p; ++m) {
         const int z = W - m;                               // the slot this order retires
@@ -109,8 +83,8 @@ __device__ __forceinline__ void wa_burg(const double *win, int W, int p, int tid
         den = wave_sum63(den);
         double rf = wa_below(f[0]), rb = wa_below(b[0]);   // the pair of the slot above this thread's last
         if (NW == 1) {
-            num = wa_lane63(num);
-            den = wa_lane63(den);
+            num = lane63(num);
+            den = lane63(den);
         } else {
             const int par = m & 1;
             if (lane == kWave - 1) {
@@ -147,67 +121,50 @@ template <int NT, int R>
 __global__ void __launch_bounds__(NT) window_ar_kernel(const WaArgs A) {
     constexpr int NW = NT / kWave;
     extern __shared__ double wa_win[];                     // the window and the zeros behind it
-    __shared__ double first[NW], e0[NW];                   // sum (x - p), sum x^2
-    __shared__ int bad[NW];
+    __shared__ double e0[NW];                              // sum x^2
     __shared__ double red[2][NW][2], edge[2][NW][2];       // burg: (num, den) and (F, B) of a wave's last lane
     __shared__ double kk[kArLags];                         // burg: k_m
     __shared__ double lag[kArLags][NW], rr[kArLags];       // yule_walker: the waves' sums, r_j
     const int tid = threadIdx.x, lane = tid & (kWave - 1), w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int W = A.W, mask = A.mask, p = A.order;
     const bool burg = A.method == OSZ_AR_BURG;
-    // (the launch holds fewer than 2^31 workgroups: a 32-bit division)
-    const unsigned per_row = (unsigned)A.nwin;
-    const int64_t c = blockIdx.x / per_row, kw = blockIdx.x % per_row;
-    const double *__restrict__ row = A.x + c * A.pitch + kw * A.step;
-    double *__restrict__ dst = A.out + c * A.row_pitch + kw;
+    const WinAt at = win_where(A);
+    const double *__restrict__ row = at.row;
+    double *__restrict__ dst = at.dst;
 
     // the window into registers (every load in flight at once), the sum about its first sample, the ballot
     const double x0 = row[0], piv = __builtin_isfinite(x0) ? x0 : 0.0;
     double xs[R];
 #pragma unroll
     for (int j = 0; j < R; ++j) xs[j] = tid + j * NT < W ? row[tid + j * NT] : 0.0;
-    double s1 = 0.0;
+    double S1[1] = {0.0};
     bool wild = false;
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         wild |= !__builtin_isfinite(xs[j]);
-        s1 += tid + j * NT < W ? xs[j] - piv : 0.0;
+        S1[0] += tid + j * NT < W ? xs[j] - piv : 0.0;
     }
-    s1 = wave_sum63(s1);
-    const bool any = __ballot(wild) != 0ull;
-    if (lane == kWave - 1) {
-        first[w] = s1;
-        bad[w] = any;
-    }
-    __syncthreads();
-    double S1 = first[0];
-    int wilds = bad[0];
-#pragma unroll
-    for (int j = 1; j < NW; ++j) {
-        S1 += first[j];
-        wilds |= bad[j];
-    }
+    const bool spoilt = win_fold<NW>(S1, wild, lane, w);
     const int pl_ref = (mask & 1) * p, pl_err = pl_ref + ((mask >> OSZ_AR_REFLECTION) & 1) * p;
     const int pl_path = pl_err + ((mask >> OSZ_AR_ERROR) & 1);
-    if (wilds) {                                           // (the whole workgroup)
-        const int planes = pl_path + ((mask >> OSZ_AR_ERROR_PATH) & 1) * (p + 1);
-        for (int pl = tid; pl < planes; pl += NT) dst[(int64_t)pl * A.plane_pitch] = __builtin_nan("");
+    if (spoilt) {                                          // (the whole workgroup)
+        win_spoilt<NT>(dst, pl_path + ((mask >> OSZ_AR_ERROR_PATH) & 1) * (p + 1), A.plane_pitch, tid);
         return;
     }
 
     // the window, centred, into LDS; zeros from W to NT R + OSZ_AR_ORDER; burg's sum x^2
-    const double mu = S1 / (double)W;
+    const double mu = S1[0] / (double)W;
     double s2 = 0.0;
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         const int t = tid + j * NT;
         if (t < W) {
             xs[j] = A.center ? (xs[j] - piv) - mu : xs[j];
-            wa_win[burg ? wa_at<true>(t) : t] = xs[j];
+            wa_win[burg ? lds_pad32(t) : t] = xs[j];
         }
         s2 = __builtin_fma(xs[j], xs[j], s2);
     }
-    for (int t = W + tid; t <= NT * R + OSZ_AR_ORDER; t += NT) wa_win[burg ? wa_at<true>(t) : t] = 0.0;
+    for (int t = W + tid; t <= NT * R + OSZ_AR_ORDER; t += NT) wa_win[burg ? lds_pad32(t) : t] = 0.0;
     s2 = wave_sum63(s2);
     if (lane == kWave - 1) e0[w] = s2;
     __syncthreads();
@@ -252,10 +209,10 @@ __global__ void __launch_bounds__(NT) window_ar_kernel(const WaArgs A) {
             k = kk[m];
         } else {
             const double term = lane < m ? a * rr[m - lane] : 0.0;
-            k = -wa_lane63(wave_sum63(term)) / E;
+            k = -lane63(wave_sum63(term)) / E;
         }
         k = (E != 0.0 && E == E) ? k : __builtin_nan("");   // a spent or lost E ends the model here
-        const double far = wa_lane_of(a, (m - lane) & (kWave - 1));
+        const double far = lane_from(a, (m - lane) & (kWave - 1));
         a = (lane >= 1 && lane < m) ? __builtin_fma(k, far, a) : lane == m ? k : a;
         E = E * (1.0 - k * k);
         if (lane == m) {
@@ -287,42 +244,21 @@ extern "C" {
 int osz_window_ar(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
                   int order, int method, int center, double *out, int64_t plane_pitch, int64_t row_pitch,
                   int64_t win0, void *stream) {
-    OSZ_REQUIRE(x && out, "osz_window_ar: null argument");
-    OSZ_REQUIRE(winsize >= 16 && winsize <= OSZ_AR_LONGEST && step >= 1,
-                "osz_window_ar: winsize=%lld (16 .. %d) step=%lld (>= 1)", (long long)winsize, OSZ_AR_LONGEST,
-                (long long)step);
-    OSZ_REQUIRE(mask >= 1 && mask < (1 << OSZ_AR_COUNT), "osz_window_ar: measure mask %d", mask);
+    static const WinRule rule = {"osz_window_ar", "measure", OSZ_AR_COUNT, 16, OSZ_AR_LONGEST};
+    const int planes = ((mask >> OSZ_AR_COEFFICIENTS) & 1) * order + ((mask >> OSZ_AR_REFLECTION) & 1) * order +
+                       ((mask >> OSZ_AR_ERROR) & 1) + ((mask >> OSZ_AR_ERROR_PATH) & 1) * (order + 1);
+    WaArgs A;
+    if (int rc = win_head(rule, planes, x, pitch, nch, n, winsize, step, mask, out, plane_pitch, row_pitch, win0, A))
+        return rc;
     OSZ_REQUIRE(order >= 1 && order <= OSZ_AR_ORDER && winsize >= 4 * (int64_t)order,
                 "osz_window_ar: order=%d (1 .. %d, winsize=%lld >= 4 order)", order, OSZ_AR_ORDER, (long long)winsize);
     OSZ_REQUIRE(method == OSZ_AR_BURG || method == OSZ_AR_YULE_WALKER, "osz_window_ar: method %d", method);
-    OSZ_REQUIRE(nch >= 1 && n >= 0 && pitch >= n && win0 >= 0, "osz_window_ar: bad sizes (nch=%d n=%lld pitch=%lld)",
-                nch, (long long)n, (long long)pitch);
-    const int64_t nwin = osz_window_count(n, winsize, step);
-    const int planes = ((mask >> OSZ_AR_COEFFICIENTS) & 1) * order + ((mask >> OSZ_AR_REFLECTION) & 1) * order +
-                       ((mask >> OSZ_AR_ERROR) & 1) + ((mask >> OSZ_AR_ERROR_PATH) & 1) * (order + 1);
-    OSZ_REQUIRE(row_pitch >= win0 + nwin && (nch == 1 || plane_pitch >= (int64_t)(nch - 1) * row_pitch + win0 + nwin) &&
-                    plane_pitch >= win0 + nwin,
-                "osz_window_ar: the result's pitches (%lld, %lld) do not hold %d planes of %d rows of %lld + %lld "
-                "windows", (long long)plane_pitch, (long long)row_pitch, planes, nch, (long long)win0, (long long)nwin);
-    OSZ_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 7) == 0,
-                "osz_window_ar: the arrays must be 8-byte aligned");
-    if (nwin == 0) return OSZ_OK;
-    OSZ_REQUIRE(nwin <= INT32_MAX / nch, "osz_window_ar: %lld workgroups are too many for one launch",
-                (long long)nwin * nch);
-    WaArgs A;
-    A.x = x;
-    A.pitch = pitch;
-    A.step = step;
-    A.nwin = nwin;
-    A.W = (int)winsize;
-    A.mask = mask;
+    if (A.nwin == 0) return OSZ_OK;
+    unsigned nblk;
+    if (int rc = win_grid(rule, A, nch, nblk)) return rc;
     A.order = order;
     A.method = method;
     A.center = center != 0;
-    A.out = out + win0;
-    A.plane_pitch = plane_pitch;
-    A.row_pitch = row_pitch;
-    const unsigned nblk = (unsigned)(nwin * nch);
     const int W = (int)winsize, NT = W >= OSZ_AR_WIDE ? 256 : kWave;
     int R = 1;                                             // samples a thread: the least power of two with NT R >= W
     while (NT * R < W) R *= 2;

@@ -23,7 +23,7 @@
 //     lane l the bins l + 64 k in that order, the lanes by wave_sum63.
 // No floating-point operation is atomic, so a window's bits depend on W, the parameters and its
 // own samples only.
-#include "common.h"
+#include "window_block.h"
 
 namespace osz {
 
@@ -37,16 +37,10 @@ constexpr int kWeOrder = 6;
 static_assert((int64_t)OSZ_WE_LONGEST * OSZ_WE_LONGEST / 2 < ((int64_t)1 << 32), "OSZ_WE_LONGEST");
 static_assert(OSZ_WE_WIDE >= 2 * kWave && kWePad >= kWave, "window_entropy_kernel");
 
-struct WeArgs {
-    const double *x;      // (nch, n) rows, row pitch `pitch`
-    int64_t pitch, step;
-    int64_t nwin;         // windows of this launch (per channel)
-    int W, mask;
+struct WeArgs : WinHead {
     int m, tol;
     double r;
     int order, delay, normalize;
-    double *out;          // already at the first window of this launch
-    int64_t plane_pitch, row_pitch;
 };
 
 // One step t along a diagonal of lag L: xt = x_t, xf = x_{t+L}.  With run the matches in a row up
@@ -90,59 +84,40 @@ template <int NT>
 __global__ void __launch_bounds__(NT) window_entropy_kernel(const WeArgs A) {
     constexpr int NW = NT / kWave;
     extern __shared__ double we_win[];                     // W + kWePad
-    __shared__ double red[NW][2];
-    __shared__ int bad[NW];
     __shared__ unsigned hist[kWeBins];
     __shared__ unsigned cnt[2];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int W = A.W;
-    const int64_t c = (int64_t)blockIdx.x / A.nwin, k = (int64_t)blockIdx.x % A.nwin;
-    const double *__restrict__ row = A.x + c * A.pitch + k * A.step;
-    double *__restrict__ dst = A.out + c * A.row_pitch + k;
+    const WinAt at = win_where(A);
+    const double *__restrict__ row = at.row;
+    double *__restrict__ dst = at.dst;
     const int planes = __builtin_popcount(A.mask);
 
     // the window into LDS, the sums about its first sample, the ballot
     const double x0 = row[0], p = __builtin_isfinite(x0) ? x0 : 0.0;
-    double s1 = 0.0, s2 = 0.0;
+    double S[2] = {0.0, 0.0};                              // sum y, sum y^2
     bool wild = false;
     for (int t = tid; t < W; t += NT) {
         const double v = row[t];
         we_win[t] = v;
         wild |= !__builtin_isfinite(v);
         const double y = v - p;
-        s1 += y;
-        s2 += y * y;
+        S[0] += y;
+        S[1] += y * y;
     }
     if (tid < kWePad) we_win[W + tid] = 0.0;
     for (int i = tid; i < kWeBins; i += NT) hist[i] = 0u;
     if (tid < 2) cnt[tid] = 0u;
-    s1 = wave_sum63(s1);
-    s2 = wave_sum63(s2);
-    const bool any = __ballot(wild) != 0ull;
-    if (lane == kWave - 1) {
-        red[w][0] = s1;
-        red[w][1] = s2;
-        bad[w] = any;
-    }
-    __syncthreads();
-    double S1 = red[0][0], S2 = red[0][1];
-    int wilds = bad[0];
-#pragma unroll
-    for (int j = 1; j < NW; ++j) {
-        S1 += red[j][0];
-        S2 += red[j][1];
-        wilds |= bad[j];
-    }
-    if (wilds) {                                           // (the whole workgroup)
-        if (tid < planes) dst[(int64_t)tid * A.plane_pitch] = __builtin_nan("");
+    if (win_fold<NW>(S, wild, lane, w)) {                  // (the whole workgroup; its barrier publishes the window too)
+        win_spoilt<NT>(dst, planes, A.plane_pitch, tid);
         return;
     }
 
     if (A.mask & 7) {
         double rho = A.r;
         if (A.tol == OSZ_WE_TOL_STD) {
-            const double rn = 1.0 / (double)W, mu = S1 * rn;
-            rho = A.r * sqrt(__builtin_fmax(S2 * rn - mu * mu, 0.0));
+            const double rn = 1.0 / (double)W, mu = S[0] * rn;
+            rho = A.r * sqrt(__builtin_fmax(S[1] * rn - mu * mu, 0.0));
         }
         // The templates are 0 .. N - 1, the lags 1 .. N - 1; task q of the N / 2 takes lag q + 1
         // and then lag N - (q + 1) (the same lag once, for the middle one of an even N).  A wave
@@ -228,11 +203,11 @@ extern "C" {
 int osz_window_entropy(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
                        int m, double r, int tolerance, int order, int64_t delay, int normalize, double *out,
                        int64_t plane_pitch, int64_t row_pitch, int64_t win0, void *stream) {
-    OSZ_REQUIRE(x && out, "osz_window_entropy: null argument");
-    OSZ_REQUIRE(winsize >= 4 && winsize <= OSZ_WE_LONGEST && step >= 1,
-                "osz_window_entropy: winsize=%lld (4 .. %d) step=%lld (>= 1)", (long long)winsize, OSZ_WE_LONGEST,
-                (long long)step);
-    OSZ_REQUIRE(mask >= 1 && mask < (1 << OSZ_WE_COUNT), "osz_window_entropy: measure mask %d", mask);
+    static const WinRule rule = {"osz_window_entropy", "measure", OSZ_WE_COUNT, 4, OSZ_WE_LONGEST};
+    WeArgs A;
+    if (int rc = win_head(rule, __builtin_popcount(mask), x, pitch, nch, n, winsize, step, mask, out, plane_pitch,
+                          row_pitch, win0, A))
+        return rc;
     OSZ_REQUIRE(m >= 1 && m <= 8 && r >= 0.0 && __builtin_isfinite(r) &&
                     (tolerance == OSZ_WE_TOL_STD || tolerance == OSZ_WE_TOL_ABSOLUTE),
                 "osz_window_entropy: m=%d (1 .. 8) r=%g (finite, >= 0) tolerance=%d (0, 1)", m, r, tolerance);
@@ -244,35 +219,15 @@ int osz_window_entropy(const double *x, int64_t pitch, int nch, int64_t n, int64
     OSZ_REQUIRE(!perm || (delay < winsize && (order - 1) * delay < winsize),
                 "osz_window_entropy: winsize=%lld holds no vector of order=%d, delay=%lld", (long long)winsize, order,
                 (long long)delay);
-    OSZ_REQUIRE(nch >= 1 && n >= 0 && pitch >= n && win0 >= 0,
-                "osz_window_entropy: bad sizes (nch=%d n=%lld pitch=%lld)", nch, (long long)n, (long long)pitch);
-    const int64_t nwin = osz_window_count(n, winsize, step);
-    OSZ_REQUIRE(row_pitch >= win0 + nwin && (nch == 1 || plane_pitch >= (int64_t)(nch - 1) * row_pitch + win0 + nwin) &&
-                    plane_pitch >= win0 + nwin,
-                "osz_window_entropy: the result's pitches (%lld, %lld) do not hold %d rows of %lld + %lld windows",
-                (long long)plane_pitch, (long long)row_pitch, nch, (long long)win0, (long long)nwin);
-    OSZ_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 7) == 0,
-                "osz_window_entropy: the arrays must be 8-byte aligned");
-    if (nwin == 0) return OSZ_OK;
-    OSZ_REQUIRE(nwin <= INT32_MAX / nch, "osz_window_entropy: %lld workgroups are too many for one launch",
-                (long long)nwin * nch);
-    WeArgs A;
-    A.x = x;
-    A.pitch = pitch;
-    A.step = step;
-    A.nwin = nwin;
-    A.W = (int)winsize;
-    A.mask = mask;
+    if (A.nwin == 0) return OSZ_OK;
+    unsigned nblk;
+    if (int rc = win_grid(rule, A, nch, nblk)) return rc;
     A.m = m;
     A.tol = tolerance;
     A.r = r;
     A.order = order;
     A.delay = perm ? (int)delay : 1;
     A.normalize = normalize;
-    A.out = out + win0;
-    A.plane_pitch = plane_pitch;
-    A.row_pitch = row_pitch;
-    const unsigned nblk = (unsigned)(nwin * nch);
     const size_t lds = (size_t)(winsize + kWePad) * sizeof(double);
     hipStream_t st = as_stream(stream);
     KernelTimer timer("window_entropy", st);

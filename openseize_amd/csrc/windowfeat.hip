@@ -21,7 +21,7 @@
 // (workgroup kernel), and when the group is done the lanes turn the sums into the features side
 // by side -- the divisions and square roots cost one lane's time for up to 64 windows -- and
 // store 64 consecutive windows of a plane in one instruction.
-#include "common.h"
+#include "window_block.h"
 
 namespace osz {
 
@@ -47,14 +47,6 @@ struct WfPivot {
 };
 
 __device__ __forceinline__ double finite_or_zero(double v) { return __builtin_isfinite(v) ? v : 0.0; }
-
-// lane L's value in every lane
-template <int L>
-__device__ __forceinline__ double lane_of(double v) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), L);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), L);
-    return __hiloint2double(hi, lo);
-}
 
 // (every lane reads the same three samples: one request)
 __device__ __forceinline__ WfPivot wf_pivot(const double *__restrict__ row) {
@@ -138,7 +130,8 @@ __device__ __forceinline__ void wf_quad(__amdgpu_buffer_rsrc_t rs, int64_t t0, i
 }
 
 // Thread tid's share of the window: samples tid, tid + NT, ...  Whole waves take every trip
-// together (the shuffles need all 64 lanes).
+// together (the shuffles need all 64 lanes).  (The callers hand over the head's 32-bit W > 0
+// zero-extended: the upper half of every 64-bit compare with it is then a constant.)
 template <int NT>
 __device__ __forceinline__ void wf_accumulate(const double *__restrict__ row, int64_t W, int tid, int lane,
                                               const WfPivot pv, WfAcc &s) {
@@ -171,8 +164,6 @@ __device__ __forceinline__ double wave_max(double v) {
     for (int off = 32; off >= 1; off >>= 1) v = __builtin_fmax(v, __shfl_xor(v, off, kWave));
     return v;
 }
-
-__device__ __forceinline__ double lane63(double v) { return lane_of<kWave - 1>(v); }
 
 // The wave's fold of a window in q[0 .. kWfSums) (the same in every lane), the crossings in zc,
 // "holds a NaN" in nan.
@@ -231,17 +222,10 @@ __device__ __forceinline__ void wf_finish(const double q[kWfSums], double zc, bo
     }
 }
 
-struct WfArgs {
-    const double *x;      // (nch, n) rows, row pitch `pitch`
-    int64_t pitch;
-    int64_t W, step;
-    int64_t nwin;         // windows of this launch (per channel)
+struct WfArgs : WinHead {
     int64_t ngroups;      // ceil(nwin / group)
     int64_t ntasks;       // nch * ngroups
     int group;            // windows one wave / workgroup works through, 1 .. 64
-    int mask;
-    double *out;          // already at the first window of this launch
-    int64_t plane_pitch, row_pitch;
 };
 
 // W < OSZ_WF_LONG: one wave per (channel, group of windows); four independent waves a workgroup.
@@ -265,7 +249,7 @@ __global__ void __launch_bounds__(256) window_wave_kernel(const WfArgs A) {
         const double *row = ch + (k0 + g) * A.step;
         const WfPivot pv = wf_pivot(row);
         WfAcc s;
-        wf_accumulate<kWave>(row, A.W, lane, lane, pv, s);
+        wf_accumulate<kWave>(row, (unsigned)A.W, lane, lane, pv, s);
         double q[kWfSums];
         int zc;
         bool nan;
@@ -296,7 +280,7 @@ __global__ void __launch_bounds__(256) window_block_kernel(const WfArgs A) {
         const double *row = ch + (k0 + g) * A.step;
         const WfPivot pv = wf_pivot(row);
         WfAcc s;
-        wf_accumulate<256>(row, A.W, w * kWave + lane, lane, pv, s);
+        wf_accumulate<256>(row, (unsigned)A.W, w * kWave + lane, lane, pv, s);
         double q[kWfSums];
         int zc;
         bool nan;
@@ -341,39 +325,21 @@ int64_t osz_window_count(int64_t n, int64_t winsize, int64_t step) {
 
 int osz_window_features(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
                         double *out, int64_t plane_pitch, int64_t row_pitch, int64_t win0, void *stream) {
-    OSZ_REQUIRE(x && out, "osz_window_features: null argument");
-    OSZ_REQUIRE(winsize >= 4 && winsize <= OSZ_WF_LONGEST && step >= 1,
-                "osz_window_features: winsize=%lld (4 .. %d) step=%lld (>= 1)", (long long)winsize, OSZ_WF_LONGEST,
-                (long long)step);
-    OSZ_REQUIRE(mask >= 1 && mask < (1 << OSZ_WF_COUNT), "osz_window_features: feature mask %d", mask);
-    OSZ_REQUIRE(nch >= 1 && n >= 0 && pitch >= n && win0 >= 0, "osz_window_features: bad sizes (nch=%d n=%lld pitch=%lld)",
-                nch, (long long)n, (long long)pitch);
-    const int64_t nwin = osz_window_count(n, winsize, step);
-    OSZ_REQUIRE(row_pitch >= win0 + nwin && (nch == 1 || plane_pitch >= (int64_t)(nch - 1) * row_pitch + win0 + nwin) &&
-                    plane_pitch >= win0 + nwin,
-                "osz_window_features: the result's pitches (%lld, %lld) do not hold %d rows of %lld + %lld windows",
-                (long long)plane_pitch, (long long)row_pitch, nch, (long long)win0, (long long)nwin);
-    OSZ_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 7) == 0,
-                "osz_window_features: the arrays must be 8-byte aligned");
+    static const WinRule rule = {"osz_window_features", "feature", OSZ_WF_COUNT, 4, OSZ_WF_LONGEST};
+    WfArgs A;
+    if (int rc = win_head(rule, __builtin_popcount(mask), x, pitch, nch, n, winsize, step, mask, out, plane_pitch,
+                          row_pitch, win0, A))
+        return rc;
+    const int64_t nwin = A.nwin;
     if (nwin == 0) return OSZ_OK;
     const bool longw = winsize >= OSZ_WF_LONG;
     // windows per wave / workgroup: as many as 64 while the launch still fills the chip
     const int64_t want = longw ? 2048 : 8192;
     int group = 64;
     while (group > 1 && nch * ((nwin + group - 1) / group) < want) group >>= 1;
-    WfArgs A;
-    A.x = x;
-    A.pitch = pitch;
-    A.W = winsize;
-    A.step = step;
-    A.nwin = nwin;
     A.ngroups = (nwin + group - 1) / group;
     A.ntasks = nch * A.ngroups;
     A.group = group;
-    A.mask = mask;
-    A.out = out + win0;
-    A.plane_pitch = plane_pitch;
-    A.row_pitch = row_pitch;
     const int64_t nblk = longw ? A.ntasks : (A.ntasks + 3) / 4;
     OSZ_REQUIRE(nblk <= INT32_MAX, "osz_window_features: %lld workgroups are too many for one launch", (long long)nblk);
     hipStream_t st = as_stream(stream);

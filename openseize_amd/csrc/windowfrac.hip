@@ -35,7 +35,7 @@
 // No floating-point operation is atomic.
 #include <cmath>
 
-#include "common.h"
+#include "window_block.h"
 
 namespace osz {
 
@@ -54,53 +54,27 @@ static_assert(OSZ_WR_WIDE <= 8 * kWave && OSZ_WR_LONGEST <= 16 * 256, "window_fr
 static_assert(kWrPad >= 256 + 2 && kWrPad >= OSZ_WR_LONGEST / 32 + 1, "kWrPad");
 static_assert(OSZ_WR_KMAX <= kWave && OSZ_WR_SCALES <= kWave, "window_fractal_kernel: one lane a k, a scale");
 
-struct WrArgs {
-    const double *x;      // (nch, n) rows, row pitch `pitch`
-    int64_t pitch, step;
-    int64_t nwin;         // windows of this launch (per channel)
-    int W, mask;
+struct WrArgs : WinHead {
     int kmax, nscale;
     double ln_n, log10_w; // ln(W - 1) and log10 W, the host's
-    double *out;          // already at the first window of this launch
-    int64_t plane_pitch, row_pitch;
     int scales[OSZ_WR_SCALES];
 };
 
-// Maximum over the 64 lanes of values >= 0, valid in lane 63: wave_sum63 with max (a lane
-// without a source reads 0).
-__device__ __forceinline__ double wave_max63(double v) {
-    v = __builtin_fmax(v, dpp_mov0<0x111>(v));
-    v = __builtin_fmax(v, dpp_mov0<0x112>(v));
-    v = __builtin_fmax(v, dpp_mov0<0x114>(v));
-    v = __builtin_fmax(v, dpp_mov0<0x118>(v));
-    v = __builtin_fmax(v, dpp_mov0<0x142>(v));
-    v = __builtin_fmax(v, dpp_mov0<0x143>(v));
-    return v;
-}
-
-// lane l's v in every lane (l a constant)
-__device__ __forceinline__ double lane_value(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
 // Inclusive prefix sum over the 64 lanes: four row_shr steps scan the 16-lane rows, then a lane
-// adds the totals of the rows below its own, in their order.
+// adds the totals of the rows below its own, in their order.  (Not ws_wave_scan of windowspec.hip,
+// which adds what row_bcast hands on, row 0 + row 1 before row 2: other bits.  Each kernel's
+// results are pinned to its own order.)
 __device__ __forceinline__ double wave_scan(double v, int lane) {
     v += dpp_mov0<0x111>(v);
     v += dpp_mov0<0x112>(v);
     v += dpp_mov0<0x114>(v);
     v += dpp_mov0<0x118>(v);
-    const double r0 = lane_value(v, 15), r1 = lane_value(v, 31), r2 = lane_value(v, 47);
+    const double r0 = lane_of<15>(v), r1 = lane_of<31>(v), r2 = lane_of<47>(v);
     v += lane >= 16 ? r0 : 0.0;
     v += lane >= 32 ? r1 : 0.0;
     v += lane >= 48 ? r2 : 0.0;
     return v;
 }
-
-// where sample t of the profile lies in LDS
-__device__ __forceinline__ int wr_at(int t) { return t + (t >> 5); }
 
 // Sum over every group of g consecutive lanes, g a power of two up to 64 and the wave's: valid in
 // the LAST lane of each group -- the first log2 g steps of wave_sum63.
@@ -115,12 +89,7 @@ __device__ __forceinline__ double group_sum(double v, int g) {
 }
 
 // the v of the last lane of its group of g, in every lane
-__device__ __forceinline__ double group_last(double v, int lane, int g) {
-    const int from = (lane | (g - 1)) << 2;
-    const int lo = __builtin_amdgcn_ds_bpermute(from, __double2loint(v));
-    const int hi = __builtin_amdgcn_ds_bpermute(from, __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
+__device__ __forceinline__ double group_last(double v, int lane, int g) { return lane_from(v, lane | (g - 1)); }
 
 // Least-squares slope of v on u over n points, the abscissa centred (one thread).
 __device__ __forceinline__ double wr_slope(const double *u, const double *v, int n) {
@@ -140,8 +109,8 @@ template <int NT, int JMAX>
 __global__ void __launch_bounds__(NT) window_fractal_kernel(const WrArgs A) {
     constexpr int NW = NT / kWave;
     extern __shared__ double wr_win[];                     // W + kWrPad: the window, then its profile
-    __shared__ double red[NW][3];                          // sum (x - p); katz's L and d
-    __shared__ int bad[NW], flips[NW];
+    __shared__ double red[NW][2];                          // katz's L and d
+    __shared__ int flips[NW];
     __shared__ double hred[OSZ_WR_KMAX][NW][2];
     __shared__ double tot[JMAX * NW];
     __shared__ double dred[OSZ_WR_SCALES][NW];
@@ -149,9 +118,9 @@ __global__ void __launch_bounds__(NT) window_fractal_kernel(const WrArgs A) {
     __shared__ int sc[OSZ_WR_SCALES];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int W = A.W, mask = A.mask;
-    const int64_t c = (int64_t)blockIdx.x / A.nwin, kw = (int64_t)blockIdx.x % A.nwin;
-    const double *__restrict__ row = A.x + c * A.pitch + kw * A.step;
-    double *__restrict__ dst = A.out + c * A.row_pitch + kw;
+    const WinAt at = win_where(A);
+    const double *__restrict__ row = at.row;
+    double *__restrict__ dst = at.dst;
     const bool higuchi = mask & (1 << OSZ_WR_HIGUCHI), dfa = mask & (1 << OSZ_WR_DFA | 1 << OSZ_WR_DFA_FLUCTUATIONS);
     const int S = dfa ? A.nscale : 0;
 
@@ -160,7 +129,7 @@ __global__ void __launch_bounds__(NT) window_fractal_kernel(const WrArgs A) {
     double xr[JMAX];
 #pragma unroll
     for (int j = 0; j < JMAX; ++j) xr[j] = 0.0;
-    double s1 = 0.0;
+    double S1[1] = {0.0};
     bool wild = false;
 #pragma unroll
     for (int j = 0; j < JMAX; ++j) {
@@ -171,26 +140,12 @@ __global__ void __launch_bounds__(NT) window_fractal_kernel(const WrArgs A) {
             wr_win[t] = v;
             xr[j] = v;
             wild |= !__builtin_isfinite(v);
-            s1 += v - p;
+            S1[0] += v - p;
         }
     }
-    s1 = wave_sum63(s1);
-    const bool any = __ballot(wild) != 0ull;
-    if (lane == kWave - 1) {
-        red[w][0] = s1;
-        bad[w] = any;
-    }
-    __syncthreads();
-    double S1 = red[0][0];
-    int wilds = bad[0];
-#pragma unroll
-    for (int j = 1; j < NW; ++j) {
-        S1 += red[j][0];
-        wilds |= bad[j];
-    }
-    if (wilds) {                                           // (the whole workgroup)
-        const int planes = __builtin_popcount(mask & 15) + ((mask >> OSZ_WR_DFA_FLUCTUATIONS) & 1) * S;
-        for (int pl = tid; pl < planes; pl += NT) dst[(int64_t)pl * A.plane_pitch] = __builtin_nan("");
+    if (win_fold<NW>(S1, wild, lane, w)) {                 // (the whole workgroup)
+        win_spoilt<NT>(dst, __builtin_popcount(mask & 15) + ((mask >> OSZ_WR_DFA_FLUCTUATIONS) & 1) * S, A.plane_pitch,
+                       tid);
         return;
     }
 
@@ -211,8 +166,8 @@ __global__ void __launch_bounds__(NT) window_fractal_kernel(const WrArgs A) {
         kl = wave_sum63(kl);
         kd = wave_max63(kd);
         if (lane == kWave - 1) {
-            red[w][1] = kl;
-            red[w][2] = kd;
+            red[w][0] = kl;
+            red[w][1] = kd;
             flips[w] = flip;
         }
     }
@@ -246,7 +201,7 @@ __global__ void __launch_bounds__(NT) window_fractal_kernel(const WrArgs A) {
 
     if (dfa) {                                             // (uniform: the barriers are the workgroup's)
         // the scan of each wave's 64 consecutive samples, in place of the samples
-        const double mu = S1 / (double)W;
+        const double mu = S1[0] / (double)W;
 #pragma unroll
         for (int j = 0; j < JMAX; ++j) {
             if (j * NT >= W) break;
@@ -266,7 +221,7 @@ __global__ void __launch_bounds__(NT) window_fractal_kernel(const WrArgs A) {
                 run += tot[j * NW + v];
             }
             const int t = tid + j * NT;
-            if (t < W) wr_win[wr_at(t)] = base + xr[j];
+            if (t < W) wr_win[lds_pad32(t)] = base + xr[j];
         }
         __syncthreads();
 
@@ -286,10 +241,10 @@ __global__ void __launch_bounds__(NT) window_fractal_kernel(const WrArgs A) {
             for (int b0 = 0; b0 < nb; b0 += per) {         // (one round unless g = 1)
                 const bool on = b0 + grp < nb;             // (a group without a box redoes the last one)
                 const int t0 = (on ? b0 + grp : nb - 1) * n;
-                const double y0 = wr_win[wr_at(t0)];
+                const double y0 = wr_win[lds_pad32(t0)];
                 double sy = 0.0, sxy = 0.0;
                 for (int i = r; i < n; i += g) {
-                    const double d = wr_win[wr_at(t0 + i)] - y0;
+                    const double d = wr_win[lds_pad32(t0 + i)] - y0;
                     sy += d;
                     sxy += ((double)i - ibar) * d;
                 }
@@ -300,7 +255,7 @@ __global__ void __launch_bounds__(NT) window_fractal_kernel(const WrArgs A) {
                 const double ic = sy * rinv, sl = sxy * sinv;
                 double rss = 0.0;
                 for (int i = r; i < n; i += g) {
-                    const double e = ((wr_win[wr_at(t0 + i)] - y0) - ic) - sl * ((double)i - ibar);
+                    const double e = ((wr_win[lds_pad32(t0 + i)] - y0) - ic) - sl * ((double)i - ibar);
                     rss += e * e;
                 }
                 rss = group_sum(rss, g);
@@ -343,11 +298,11 @@ __global__ void __launch_bounds__(NT) window_fractal_kernel(const WrArgs A) {
     if (tid != 0) return;
     if (higuchi) dst[0] = wr_slope(hu, hv, A.kmax);
     if (mask & (1 << OSZ_WR_KATZ)) {
-        double L = red[0][1], d = red[0][2];
+        double L = red[0][0], d = red[0][1];
 #pragma unroll
         for (int j = 1; j < NW; ++j) {
-            L += red[j][1];
-            d = __builtin_fmax(d, red[j][2]);
+            L += red[j][0];
+            d = __builtin_fmax(d, red[j][1]);
         }
         dst[(int64_t)__builtin_popcount(mask & 1) * A.plane_pitch] = A.ln_n / (A.ln_n + log(d / L));
     }
@@ -371,16 +326,15 @@ extern "C" {
 int osz_window_fractal(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
                        int kmax, const int *scales, int nscales, double *out, int64_t plane_pitch, int64_t row_pitch,
                        int64_t win0, void *stream) {
-    OSZ_REQUIRE(x && out, "osz_window_fractal: null argument");
-    OSZ_REQUIRE(winsize >= 8 && winsize <= OSZ_WR_LONGEST && step >= 1,
-                "osz_window_fractal: winsize=%lld (8 .. %d) step=%lld (>= 1)", (long long)winsize, OSZ_WR_LONGEST,
-                (long long)step);
-    OSZ_REQUIRE(mask >= 1 && mask < (1 << OSZ_WR_COUNT), "osz_window_fractal: measure mask %d", mask);
+    static const WinRule rule = {"osz_window_fractal", "measure", OSZ_WR_COUNT, 8, OSZ_WR_LONGEST};
+    const int planes = __builtin_popcount(mask & 15) + ((mask >> OSZ_WR_DFA_FLUCTUATIONS) & 1) * nscales;
+    WrArgs A;
+    if (int rc = win_head(rule, planes, x, pitch, nch, n, winsize, step, mask, out, plane_pitch, row_pitch, win0, A))
+        return rc;
     const bool higuchi = (mask & (1 << OSZ_WR_HIGUCHI)) != 0;
     const bool dfa = (mask & (1 << OSZ_WR_DFA | 1 << OSZ_WR_DFA_FLUCTUATIONS)) != 0;
     OSZ_REQUIRE(!higuchi || (kmax >= 2 && kmax <= OSZ_WR_KMAX && winsize >= 2 * (int64_t)kmax),
                 "osz_window_fractal: kmax=%d (2 .. %d, winsize=%lld >= 2 kmax)", kmax, OSZ_WR_KMAX, (long long)winsize);
-    WrArgs A;
     memset(A.scales, 0, sizeof A.scales);
     if (dfa) {
         OSZ_REQUIRE(scales && nscales >= 2 && nscales <= OSZ_WR_SCALES, "osz_window_fractal: %d scales (2 .. %d)",
@@ -392,34 +346,13 @@ int osz_window_fractal(const double *x, int64_t pitch, int nch, int64_t n, int64
             A.scales[s] = scales[s];
         }
     }
-    OSZ_REQUIRE(nch >= 1 && n >= 0 && pitch >= n && win0 >= 0,
-                "osz_window_fractal: bad sizes (nch=%d n=%lld pitch=%lld)", nch, (long long)n, (long long)pitch);
-    const int64_t nwin = osz_window_count(n, winsize, step);
-    const int planes = __builtin_popcount(mask & 15) + ((mask >> OSZ_WR_DFA_FLUCTUATIONS) & 1) * nscales;
-    OSZ_REQUIRE(row_pitch >= win0 + nwin && (nch == 1 || plane_pitch >= (int64_t)(nch - 1) * row_pitch + win0 + nwin) &&
-                    plane_pitch >= win0 + nwin,
-                "osz_window_fractal: the result's pitches (%lld, %lld) do not hold %d planes of %d rows of %lld + "
-                "%lld windows", (long long)plane_pitch, (long long)row_pitch, planes, nch, (long long)win0,
-                (long long)nwin);
-    OSZ_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 7) == 0,
-                "osz_window_fractal: the arrays must be 8-byte aligned");
-    if (nwin == 0) return OSZ_OK;
-    OSZ_REQUIRE(nwin <= INT32_MAX / nch, "osz_window_fractal: %lld workgroups are too many for one launch",
-                (long long)nwin * nch);
-    A.x = x;
-    A.pitch = pitch;
-    A.step = step;
-    A.nwin = nwin;
-    A.W = (int)winsize;
-    A.mask = mask;
+    if (A.nwin == 0) return OSZ_OK;
+    unsigned nblk;
+    if (int rc = win_grid(rule, A, nch, nblk)) return rc;
     A.kmax = higuchi ? kmax : 2;
     A.nscale = dfa ? nscales : 0;
     A.ln_n = std::log((double)(winsize - 1));
     A.log10_w = std::log10((double)winsize);
-    A.out = out + win0;
-    A.plane_pitch = plane_pitch;
-    A.row_pitch = row_pitch;
-    const unsigned nblk = (unsigned)(nwin * nch);
     const size_t lds = (size_t)(winsize + kWrPad) * sizeof(double);
     hipStream_t st = as_stream(stream);
     KernelTimer timer("window_fractal", st);

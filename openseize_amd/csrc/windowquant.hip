@@ -21,7 +21,7 @@
 //     |x - median| and the same network runs again (the loop below: the network is emitted once).
 // A key compares as an integer, every measure is a selection followed by at most four IEEE
 // operations: a window's bits depend on W, q and its own samples only.
-#include "common.h"
+#include "window_block.h"
 
 namespace osz {
 
@@ -35,15 +35,10 @@ static_assert(OSZ_WQ_NARROWEST == kWave && OSZ_WQ_WAVE == 8 * kWave && OSZ_WQ_LO
                   OSZ_WQ_QMOST <= kWave,
               "window_quantiles_kernel");
 
-struct WqArgs {
-    const double *x;      // (nch, n) rows, row pitch `pitch`
-    int64_t pitch, step;
-    int64_t nwin;         // windows of this launch (per channel)
-    int W, mask, nq;
+struct WqArgs : WinHead {
+    int nq;
     int lo[OSZ_WQ_QMOST];       // floor(q (W - 1))
     double g[OSZ_WQ_QMOST];     // q (W - 1) - lo
-    double *out;          // already at the first window of this launch
-    int64_t plane_pitch, row_pitch;
 };
 
 __device__ __forceinline__ wq_key wq_encode(double v) {
@@ -170,14 +165,15 @@ __global__ void __launch_bounds__(NT) window_quantiles_kernel(const WqArgs A) {
     __shared__ int bad[NW];
     const int t = threadIdx.x, lane = t & (kWave - 1);
     const int W = A.W;
-    const int64_t c = (int64_t)blockIdx.x / A.nwin, k = (int64_t)blockIdx.x % A.nwin;
-    const double *__restrict__ row = A.x + c * A.pitch + k * A.step;
-    double *__restrict__ dst = A.out + c * A.row_pitch + k;
+    const WinAt at = win_where(A);
+    const double *__restrict__ row = at.row;
+    double *__restrict__ dst = at.dst;
     const bool want_median = A.mask & (1 << OSZ_WQ_MEDIAN), want_mad = A.mask & (1 << OSZ_WQ_MAD);
     const int nq = (A.mask & (1 << OSZ_WQ_QUANTILE)) ? A.nq : 0;
     const int p_mad = want_median ? 1 : 0, p_q = p_mad + (want_mad ? 1 : 0);
 
-    // the window, coalesced; the ballot for NaN
+    // the window, coalesced; the ballot for NaN (an infinity sorts like any value, and there is no
+    // sum to fold: not win_fold)
     wq_key a[K];
     bool wild = false;
 #pragma unroll
@@ -198,7 +194,7 @@ __global__ void __launch_bounds__(NT) window_quantiles_kernel(const WqArgs A) {
         for (int j = 0; j < NW; ++j) any |= bad[j] != 0;
     }
     if (any) {                                             // (the whole workgroup)
-        if (t < p_q + nq) dst[(int64_t)t * A.plane_pitch] = __builtin_nan("");
+        win_spoilt<NT>(dst, p_q + nq, A.plane_pitch, t);
         return;
     }
 
@@ -251,17 +247,14 @@ extern "C" {
 int osz_window_quantiles(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
                          const double *q, int nq, double *out, int64_t plane_pitch, int64_t row_pitch, int64_t win0,
                          void *stream) {
-    OSZ_REQUIRE(x && out, "osz_window_quantiles: null argument");
-    OSZ_REQUIRE(winsize >= 4 && winsize <= OSZ_WQ_LONGEST && step >= 1,
-                "osz_window_quantiles: winsize=%lld (4 .. %d) step=%lld (>= 1)", (long long)winsize, OSZ_WQ_LONGEST,
-                (long long)step);
-    OSZ_REQUIRE(mask >= 1 && mask < (1 << OSZ_WQ_COUNT), "osz_window_quantiles: measure mask %d", mask);
+    static const WinRule rule = {"osz_window_quantiles", "measure", OSZ_WQ_COUNT, 4, OSZ_WQ_LONGEST};
+    const int planes = __builtin_popcount(mask & 3) + ((mask >> OSZ_WQ_QUANTILE) & 1) * nq;
+    WqArgs A;
+    if (int rc = win_head(rule, planes, x, pitch, nch, n, winsize, step, mask, out, plane_pitch, row_pitch, win0, A))
+        return rc;
     const bool quant = (mask & (1 << OSZ_WQ_QUANTILE)) != 0;
     OSZ_REQUIRE(!quant || (q && nq >= 1 && nq <= OSZ_WQ_QMOST), "osz_window_quantiles: %d quantiles (1 .. %d)%s", nq,
                 OSZ_WQ_QMOST, quant && !q ? ", q is null" : "");
-    OSZ_REQUIRE(nch >= 1 && n >= 0 && pitch >= n && win0 >= 0,
-                "osz_window_quantiles: bad sizes (nch=%d n=%lld pitch=%lld)", nch, (long long)n, (long long)pitch);
-    WqArgs A;
     A.nq = quant ? nq : 0;
     for (int j = 0; j < OSZ_WQ_QMOST; ++j) {
         A.lo[j] = 0;
@@ -273,28 +266,9 @@ int osz_window_quantiles(const double *x, int64_t pitch, int nch, int64_t n, int
         A.lo[j] = (int)lo;
         A.g[j] = h - lo;
     }
-    const int64_t nwin = osz_window_count(n, winsize, step);
-    const int planes = __builtin_popcount(mask & 3) + A.nq;
-    OSZ_REQUIRE(row_pitch >= win0 + nwin && (nch == 1 || plane_pitch >= (int64_t)(nch - 1) * row_pitch + win0 + nwin) &&
-                    plane_pitch >= win0 + nwin,
-                "osz_window_quantiles: the result's pitches (%lld, %lld) do not hold %d rows of %lld + %lld windows "
-                "in each of %d planes",
-                (long long)plane_pitch, (long long)row_pitch, nch, (long long)win0, (long long)nwin, planes);
-    OSZ_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 7) == 0,
-                "osz_window_quantiles: the arrays must be 8-byte aligned");
-    if (nwin == 0) return OSZ_OK;
-    OSZ_REQUIRE(nwin <= INT32_MAX / nch, "osz_window_quantiles: %lld workgroups are too many for one launch",
-                (long long)nwin * nch);
-    A.x = x;
-    A.pitch = pitch;
-    A.step = step;
-    A.nwin = nwin;
-    A.W = (int)winsize;
-    A.mask = mask;
-    A.out = out + win0;
-    A.plane_pitch = plane_pitch;
-    A.row_pitch = row_pitch;
-    const unsigned nblk = (unsigned)(nwin * nch);
+    if (A.nwin == 0) return OSZ_OK;
+    unsigned nblk;
+    if (int rc = win_grid(rule, A, nch, nblk)) return rc;
     int wpad = OSZ_WQ_NARROWEST;
     while (wpad < winsize) wpad <<= 1;
     hipStream_t st = as_stream(stream);

@@ -44,18 +44,12 @@ struct WsArgs {
     int64_t plane_pitch, row_pitch;
 };
 
-__device__ __forceinline__ double ws_lane63(double v) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-    return __hiloint2double(hi, lo);
-}
-
 // The sums of v[0 .. N) over the workgroup, in every thread: wave_sum63, then the waves in turn.
 template <int NT, int N>
 __device__ __forceinline__ void ws_block_sum(double (&v)[N], double *red, int lane, int w) {
     constexpr int NW = NT / kWave;
 #pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = ws_lane63(wave_sum63(v[i]));
+    for (int i = 0; i < N; ++i) v[i] = lane63(wave_sum63(v[i]));
     if constexpr (NW > 1) {
         if (lane == 0)
 #pragma unroll
@@ -74,6 +68,8 @@ __device__ __forceinline__ void ws_block_sum(double (&v)[N], double *red, int la
 
 // Inclusive sums over the lanes of a wave: row_shr 1, 2, 4, 8 inside the rows of 16 (lanes without
 // a source add 0), then row_bcast:15 into the odd rows and row_bcast:31 into the upper half.
+// (Not wave_scan of windowfrac.hip, which adds the totals of the rows below by readlane, in row
+// order: other bits.  Each kernel's results are pinned to its own order.)
 __device__ __forceinline__ double ws_wave_scan(double v, int lane) {
     v += dpp_mov0<0x111>(v);
     v += dpp_mov0<0x112>(v);
@@ -92,11 +88,9 @@ __device__ __forceinline__ void ws_block_scan(double s, double *red, int lane, i
     constexpr int NW = NT / kWave;
     const double inc = ws_wave_scan(s, lane);
     // the lane below: row_shr:1 inside a row, the last lane of the row before across rows
-    const int below = (lane + 63) & 63;
-    const int lo = __builtin_amdgcn_ds_bpermute(below << 2, __double2loint(inc));
-    const int hi = __builtin_amdgcn_ds_bpermute(below << 2, __double2hiint(inc));
-    excl = lane ? __hiloint2double(hi, lo) : 0.0;
-    total = ws_lane63(inc);
+    const double below = lane_from(inc, (lane + 63) & 63);
+    excl = lane ? below : 0.0;
+    total = lane63(inc);
     if constexpr (NW > 1) {
         if (lane == 0) red[w] = total;
         __syncthreads();

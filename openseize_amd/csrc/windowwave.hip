@@ -41,7 +41,7 @@
 // multiply-adds in the order of k.  No floating-point operation is atomic.
 #include <cmath>
 
-#include "common.h"
+#include "window_block.h"
 
 namespace osz {
 
@@ -52,27 +52,14 @@ static_assert(OSZ_WW_WIDE <= 2 * 4 * kWave && OSZ_WW_LONGEST <= 2 * 8 * 256, "wi
 static_assert(OSZ_WW_TAPS % 2 == 0 && 2 * OSZ_WW_TAPS <= kWave && kWwBands <= kWave,
               "window_wavelet_kernel: taps in pairs, one lane a filter value, one lane a band");
 
-struct WwArgs {
-    const double *x;      // (nch, n) rows, row pitch `pitch`
-    int64_t pitch, step;
-    int64_t nwin;         // windows of this launch (per channel)
-    int W, mask;
+struct WwArgs : WinHead {
     int pairs, levels;    // taps / 2, J
     int center, normalize;
     double ln_b;          // ln(J + 1), the host's
     double rw;            // 1 / W
     double rn[OSZ_WW_LEVELS + 1];   // 1 / the coefficients of band b
-    double *out;
-    int64_t plane_pitch, row_pitch;
     double f[OSZ_WW_TAPS / 2][4];   // h_k, h_{k+1}, g_k, g_{k+1} for k = 0, 2, ..; zeros behind the taps
 };
-
-// lane 63's v in every lane
-__device__ __forceinline__ double ww_lane63(double v) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), kWave - 1);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), kWave - 1);
-    return __hiloint2double(hi, lo);
-}
 
 // The sum, over the wave's lanes that hold one, of the Q values of c: in lane 63.
 template <int Q, int NT>
@@ -110,8 +97,6 @@ template <int NT, int Q>
 __global__ void __launch_bounds__(NT) window_wavelet_kernel(const WwArgs A) {
     constexpr int NW = NT / kWave;
     extern __shared__ __align__(16) double ww_lds[];       // W + W / 2: the window, a^1; a^2, a^3 ..
-    __shared__ double first[NW];                           // sum (x - p)
-    __shared__ int bad[NW];
     __shared__ double bsum[kWwBands][NW];                  // a band's sum
     __shared__ double bmom[kWwBands][NW][3];               // its sum c^2, sum |c|, sum (c - mean)^2
     __shared__ double eb[kWwBands], et[kWwBands];
@@ -119,11 +104,9 @@ __global__ void __launch_bounds__(NT) window_wavelet_kernel(const WwArgs A) {
     const int tid = threadIdx.x, lane = tid & (kWave - 1), w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int W = A.W, mask = A.mask, J = A.levels, B = J + 1, pairs = A.pairs;
     const bool want_abs = mask & (1 << OSZ_WW_MEAN_ABS), want_std = mask & (1 << OSZ_WW_STD);
-    // (the launch holds fewer than 2^31 workgroups: a 32-bit division)
-    const unsigned per_row = (unsigned)A.nwin;
-    const int64_t c = blockIdx.x / per_row, kw = blockIdx.x % per_row;
-    const double *__restrict__ row = A.x + c * A.pitch + kw * A.step;
-    double *__restrict__ dst = A.out + c * A.row_pitch + kw;
+    const WinAt at = win_where(A);
+    const double *__restrict__ row = at.row;
+    double *__restrict__ dst = at.dst;
 
     // the window into registers (every load in flight at once), the sum about its first sample, the
     // ballot; the filters into LDS
@@ -132,34 +115,20 @@ __global__ void __launch_bounds__(NT) window_wavelet_kernel(const WwArgs A) {
 #pragma unroll
     for (int q = 0; q < 2 * Q; ++q) xr[q] = q * NT < W && tid + q * NT < W ? row[tid + q * NT] : 0.0;
     if (tid < 2 * OSZ_WW_TAPS) ww_taps[tid >> 2][tid & 3] = A.f[tid >> 2][tid & 3];
-    double s1 = 0.0;
+    double S1[1] = {0.0};
     bool wild = false;
 #pragma unroll
     for (int q = 0; q < 2 * Q; ++q) {
         if (q * NT >= W) break;
         wild |= !__builtin_isfinite(xr[q]);
-        s1 += tid + q * NT < W ? xr[q] - p : 0.0;
+        S1[0] += tid + q * NT < W ? xr[q] - p : 0.0;
     }
-    s1 = wave_sum63(s1);
-    const bool any = __ballot(wild) != 0ull;
-    if (lane == kWave - 1) {
-        first[w] = s1;
-        bad[w] = any;
-    }
-    __syncthreads();
-    double S1 = first[0];
-    int wilds = bad[0];
-#pragma unroll
-    for (int j = 1; j < NW; ++j) {
-        S1 += first[j];
-        wilds |= bad[j];
-    }
-    if (wilds) {                                           // (the whole workgroup)
+    if (win_fold<NW>(S1, wild, lane, w)) {                 // (the whole workgroup)
         const int planes = __builtin_popcount(mask & ~(1 << OSZ_WW_ENTROPY)) * B + ((mask >> OSZ_WW_ENTROPY) & 1);
-        for (int pl = tid; pl < planes; pl += NT) dst[(int64_t)pl * A.plane_pitch] = __builtin_nan("");
+        win_spoilt<NT>(dst, planes, A.plane_pitch, tid);
         return;
     }
-    const double mu = S1 * A.rw;
+    const double mu = S1[0] * A.rw;
 #pragma unroll
     for (int q = 0; q < 2 * Q; ++q) {                      // a^0
         if (q * NT >= W) break;
@@ -219,8 +188,8 @@ __global__ void __launch_bounds__(NT) window_wavelet_kernel(const WwArgs A) {
         if (solo) {
             wave_lds_fence();                              // a^{j+1}, wave 0's own
             if (want_std) {
-                md = ww_lane63(sd);
-                ma = ww_lane63(sa);
+                md = lane63(sd);
+                ma = lane63(sa);
             }
         } else {
             if (want_std && lane == kWave - 1) {
@@ -308,42 +277,27 @@ extern "C" {
 int osz_window_wavelet(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
                        const double *lo, int taps, int levels, int center, int normalize, double *out,
                        int64_t out_plane, int64_t out_pitch, void *stream) {
-    OSZ_REQUIRE(x && out && lo, "osz_window_wavelet: null argument");
-    OSZ_REQUIRE(winsize >= 8 && winsize <= OSZ_WW_LONGEST && step >= 1,
-                "osz_window_wavelet: winsize=%lld (8 .. %d) step=%lld (>= 1)", (long long)winsize, OSZ_WW_LONGEST,
-                (long long)step);
-    OSZ_REQUIRE(mask >= 1 && mask < (1 << OSZ_WW_COUNT), "osz_window_wavelet: feature mask %d", mask);
+    static const WinRule rule = {"osz_window_wavelet", "feature", OSZ_WW_COUNT, 8, OSZ_WW_LONGEST};
+    const int B = levels + 1;
+    const int planes = __builtin_popcount(mask & ~(1 << OSZ_WW_ENTROPY)) * B + ((mask >> OSZ_WW_ENTROPY) & 1);
+    WwArgs A;
+    if (int rc = win_head(rule, planes, x, pitch, nch, n, winsize, step, mask, out, out_plane, out_pitch, 0, A))
+        return rc;
+    OSZ_REQUIRE(lo, "osz_window_wavelet: null argument");
     OSZ_REQUIRE(taps >= 2 && taps <= OSZ_WW_TAPS && taps % 2 == 0, "osz_window_wavelet: %d taps (even, 2 .. %d)", taps,
                 OSZ_WW_TAPS);
     OSZ_REQUIRE(levels >= 1 && levels <= OSZ_WW_LEVELS && winsize % ((int64_t)1 << levels) == 0,
                 "osz_window_wavelet: levels=%d (1 .. %d, winsize=%lld a multiple of 2^levels)", levels, OSZ_WW_LEVELS,
                 (long long)winsize);
-    OSZ_REQUIRE(nch >= 1 && n >= 0 && pitch >= n, "osz_window_wavelet: bad sizes (nch=%d n=%lld pitch=%lld)", nch,
-                (long long)n, (long long)pitch);
-    const int64_t nwin = osz_window_count(n, winsize, step);
-    const int B = levels + 1;
-    const int planes = __builtin_popcount(mask & ~(1 << OSZ_WW_ENTROPY)) * B + ((mask >> OSZ_WW_ENTROPY) & 1);
-    OSZ_REQUIRE(out_pitch >= nwin && out_plane >= (int64_t)(nch - 1) * out_pitch + nwin,
-                "osz_window_wavelet: the result's pitches (%lld, %lld) do not hold %d planes of %d rows of %lld windows",
-                (long long)out_plane, (long long)out_pitch, planes, nch, (long long)nwin);
-    OSZ_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 7) == 0,
-                "osz_window_wavelet: the arrays must be 8-byte aligned");
-    if (nwin == 0) return OSZ_OK;
-    OSZ_REQUIRE(nwin <= INT32_MAX / nch, "osz_window_wavelet: %lld workgroups are too many for one launch",
-                (long long)nwin * nch);
-    WwArgs A;
+    if (A.nwin == 0) return OSZ_OK;
+    unsigned nblk;
+    if (int rc = win_grid(rule, A, nch, nblk)) return rc;
     memset(A.f, 0, sizeof A.f);
     for (int k = 0; k < taps; ++k) {
         OSZ_REQUIRE(std::isfinite(lo[k]), "osz_window_wavelet: tap %d is not finite", k);
         A.f[k / 2][k % 2] = lo[k];
         A.f[k / 2][2 + k % 2] = (k % 2 ? -1.0 : 1.0) * lo[taps - 1 - k];     // g_k = (-1)^k h_{L-1-k}
     }
-    A.x = x;
-    A.pitch = pitch;
-    A.step = step;
-    A.nwin = nwin;
-    A.W = (int)winsize;
-    A.mask = mask;
     A.pairs = taps / 2;
     A.levels = levels;
     A.center = center != 0;
@@ -352,10 +306,6 @@ int osz_window_wavelet(const double *x, int64_t pitch, int nch, int64_t n, int64
     A.rw = 1.0 / (double)winsize;
     memset(A.rn, 0, sizeof A.rn);
     for (int b = 0; b < B; ++b) A.rn[b] = 1.0 / (double)(winsize >> (b < levels ? b + 1 : levels));
-    A.out = out;
-    A.plane_pitch = out_plane;
-    A.row_pitch = out_pitch;
-    const unsigned nblk = (unsigned)(nwin * nch);
     const size_t lds = (size_t)(winsize + winsize / 2) * sizeof(double);
     hipStream_t st = as_stream(stream);
     KernelTimer timer("window_wavelet", st);

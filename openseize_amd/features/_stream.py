@@ -146,6 +146,20 @@ def _launches(who, pro, W, step, kind, rows, window_bytes):
         raise ValueError(f"{who}: the stream ended before one window of {W} samples was full")
 
 
+def _planes(who, pro, W, step, kind, layout, count, launch):
+    """The launches of a per-channel function that writes ``count`` planes per window: for every
+    ``(x, n, host)`` of ``_launches``, ``launch(x, out)`` fills ``out``, a float64 (count, nch, n)
+    CUDA tensor allocated here, which goes down to the host if ``host``.  Returns ``(parts, host)``,
+    what ``_result`` takes."""
+    nch = layout.nch
+    parts, host = [], None
+    for x, n, host in _launches(who, pro, W, step, kind, layout.to2d, 8 * count * nch):
+        out = dev.torch.empty((count, nch, n), dtype=dev.torch.float64, device=x.device)
+        launch(x, out)
+        parts.append(out.cpu().numpy() if host else out)
+    return parts, host
+
+
 def _result(parts, host, layout, asked, names, where):
     """``(nwin, F)`` of a per-channel function from ``parts``, the (planes, nch, n) results of its
     launches: ndarrays if ``host``, else CUDA tensors.  Every plane gets the layout of the data

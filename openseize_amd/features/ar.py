@@ -87,7 +87,6 @@ def window_ar(data, winsize, step=None, measures=("coefficients", "error"), orde
         raise ValueError(f"window_ar: unknown method {method!r}: choose from {AR_METHODS}")
     kind = _stream._real_only(who)
     pro, layout = _stream._open(who, data, axis, chunksize, W, kind)
-    nch = layout.nch
     stacked = {"coefficients": p, "reflection": p, "error": None, "error_path": p + 1}
     where, count = {}, 0                                     # the planes a launch writes
     for f in WINDOW_ARS:
@@ -95,9 +94,6 @@ def window_ar(data, winsize, step=None, measures=("coefficients", "error"), orde
             where[f] = (count, stacked[f])
             count += stacked[f] or 1
     mask = dev.name_mask(_lib.WINDOW_AR, where)
-    parts, host = [], None
-    for x, n, host in _stream._launches(who, pro, W, step, kind, layout.to2d, 8 * count * nch):
-        out = dev.torch.empty((count, nch, n), dtype=dev.torch.float64, device=x.device)
-        dev.window_ar(x, W, step, mask, p, method, center, out)
-        parts.append(out.cpu().numpy() if host else out)
+    parts, host = _stream._planes(who, pro, W, step, kind, layout, count,
+                                  lambda x, out: dev.window_ar(x, W, step, mask, p, method, center, out))
     return _stream._result(parts, host, layout, measures, names, where)

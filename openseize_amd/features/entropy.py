@@ -84,12 +84,8 @@ def window_entropy(data, winsize, step=None, measures=("sample", "permutation"),
                          f"(order - 1) delay = {(order - 1) * delay}, got {W}")
     kind = _stream._real_only(who)
     pro, layout = _stream._open(who, data, axis, chunksize, W, kind)
-    nch = layout.nch
     planes = [f for f in WINDOW_ENTROPIES if f in names]     # the planes a launch writes
     mask = dev.name_mask(_lib.WINDOW_ENTROPY, planes)
-    parts, host = [], None
-    for x, n, host in _stream._launches(who, pro, W, step, kind, layout.to2d, 8 * len(planes) * nch):
-        out = dev.torch.empty((len(planes), nch, n), dtype=dev.torch.float64, device=x.device)
-        dev.window_entropy(x, W, step, mask, m, r, tolerance, order, delay, normalize, out)
-        parts.append(out.cpu().numpy() if host else out)
+    parts, host = _stream._planes(who, pro, W, step, kind, layout, len(planes),
+                                  lambda x, out: dev.window_entropy(x, W, step, mask, m, r, tolerance, order, delay, normalize, out))
     return _stream._result(parts, host, layout, measures, names, {f: (i, None) for i, f in enumerate(planes)})

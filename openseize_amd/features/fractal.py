@@ -116,16 +116,12 @@ def window_fractal(data, winsize, step=None, measures=("higuchi", "dfa"), kmax=8
     ns = _scales(scales, W) if any(f in _DFA for f in names) else ()
     kind = _stream._real_only(who)
     pro, layout = _stream._open(who, data, axis, chunksize, W, kind)
-    nch = layout.nch
     where, count = {}, 0                                     # the planes a launch writes
     for f in WINDOW_FRACTALS:
         if f in names:
             where[f] = (count, len(ns)) if f == "dfa_fluctuations" else (count, None)
             count += len(ns) if f == "dfa_fluctuations" else 1
     mask = dev.name_mask(_lib.WINDOW_FRACTAL, where)
-    parts, host = [], None
-    for x, n, host in _stream._launches(who, pro, W, step, kind, layout.to2d, 8 * count * nch):
-        out = dev.torch.empty((count, nch, n), dtype=dev.torch.float64, device=x.device)
-        dev.window_fractal(x, W, step, mask, kmax, ns, out)
-        parts.append(out.cpu().numpy() if host else out)
+    parts, host = _stream._planes(who, pro, W, step, kind, layout, count,
+                                  lambda x, out: dev.window_fractal(x, W, step, mask, kmax, ns, out))
     return _stream._result(parts, host, layout, measures, names, where)

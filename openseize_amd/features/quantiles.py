@@ -88,16 +88,12 @@ def window_quantiles(data, winsize, step=None, measures=("median", "mad"), q=(0.
     qs, scalar = _probabilities(q) if "quantile" in names else ([], True)
     kind = _stream._real_only(who)
     pro, layout = _stream._open(who, data, axis, chunksize, W, kind)
-    nch = layout.nch
     present = [f for f in WINDOW_QUANTILES if f in names]    # the measures a launch writes, in the kernel's order
     mask = dev.name_mask(_lib.WINDOW_QUANTILE, present)
     width = {f: len(qs) if f == "quantile" else 1 for f in present}
     where = {f: (sum(width[g] for g in present[:i]), None if f != "quantile" or scalar else len(qs))
              for i, f in enumerate(present)}
     nplanes = sum(width.values())
-    parts, host = [], None
-    for x, n, host in _stream._launches(who, pro, W, step, kind, layout.to2d, 8 * nplanes * nch):
-        out = dev.torch.empty((nplanes, nch, n), dtype=dev.torch.float64, device=x.device)
-        dev.window_quantiles(x, W, step, mask, qs, out)
-        parts.append(out.cpu().numpy() if host else out)
+    parts, host = _stream._planes(who, pro, W, step, kind, layout, nplanes,
+                                  lambda x, out: dev.window_quantiles(x, W, step, mask, qs, out))
     return _stream._result(parts, host, layout, measures, names, where)

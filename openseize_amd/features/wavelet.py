@@ -188,9 +188,6 @@ def window_wavelet(data, winsize, step=None, features=("relative", "entropy"), w
             where[f] = (count, B) if f in _PER_BAND else (count, None)
             count += B if f in _PER_BAND else 1
     mask = dev.name_mask(_lib.WINDOW_WAVELET, where)
-    parts, host = [], None
-    for x, n, host in _stream._launches(who, pro, W, step, kind, layout.to2d, 8 * count * nch):
-        out = dev.torch.empty((count, nch, n), dtype=dev.torch.float64, device=x.device)
-        dev.window_wavelet(x, W, step, mask, h, J, center, normalize, out)
-        parts.append(out.cpu().numpy() if host else out)
+    parts, host = _stream._planes(who, pro, W, step, kind, layout, count,
+                                  lambda x, out: dev.window_wavelet(x, W, step, mask, h, J, center, normalize, out))
     return _stream._result(parts, host, layout, features, names, where)

@@ -64,12 +64,8 @@ def window_features(data, winsize, step=None, features=("line_length", "var"), a
     step = W if step is None else _stream._size(step, 1, None, who, "step")
     kind = _stream._real_only(who)
     pro, layout = _stream._open(who, data, axis, chunksize, W, kind)
-    nch = layout.nch
     order = [f for f in WINDOW_FEATURES if f in names]       # the planes a launch writes
     mask = dev.name_mask(_lib.WINDOW_FEATURE, order)
-    parts, host = [], None
-    for x, n, host in _stream._launches(who, pro, W, step, kind, layout.to2d, 8 * len(order) * nch):
-        out = dev.torch.empty((len(order), nch, n), dtype=dev.torch.float64, device=x.device)
-        dev.window_features(x, W, step, mask, out)
-        parts.append(out.cpu().numpy() if host else out)
+    parts, host = _stream._planes(who, pro, W, step, kind, layout, len(order),
+                                  lambda x, out: dev.window_features(x, W, step, mask, out))
     return _stream._result(parts, host, layout, features, names, {f: (i, None) for i, f in enumerate(order)})
