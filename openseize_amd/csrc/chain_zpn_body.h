@@ -52,7 +52,7 @@ namespace osz {
 //                        previous block's (the caller alternates between two such arrays)
 //   knu[r][q], q < NM    this block's nu (rows behind the first are read for the slow modes only)
 // M's rows: Re mu [NS], Im mu [NS], Re nu [NM], Im nu [NM].  l256[q] = lambda_q^256.
-template <int NM, int NS, int PER, int RM, bool ZP>
+template <int NM, int NS, int PER, int RM, bool ZP, bool ENDS>
 __device__ __forceinline__ void zpn_fit_kappa_n(int tt, int R, const double *fitbuf, const double *mtab,
                                                 const double *l256, double *kmu, double *knu) {
     constexpr int ns = 16 * PER;
@@ -91,31 +91,48 @@ __device__ __forceinline__ void zpn_fit_kappa_n(int tt, int R, const double *fit
     if (p16 == 15 && valid) {
         const double lr = l256[q * 2 + 0], li = l256[q * 2 + 1];
         double kr = sr, ki = si;
+        if (ENDS) {
+            // (one destination and one row stride per lane, chosen once: a choice per row costs
+            // the wave two selects and an address; the rows end at the first r >= R)
+            double *kd = is_mu ? kmu + q * 2 : knu + q * 2;
+            const int ks = is_mu ? NS * 2 : NM * 2;
 #pragma unroll
-        for (int r = 0; r < RM; ++r) {
-            if (r < R) {
-                if (is_mu) {
-                    kmu[(r * NS + q) * 2 + 0] = kr;
-                    kmu[(r * NS + q) * 2 + 1] = ki;
-                } else {
-                    knu[(r * NM + q) * 2 + 0] = kr;
-                    knu[(r * NM + q) * 2 + 1] = ki;
-                }
+            for (int r = 0; r < RM; ++r) {
+                if (r >= R) break;
+                kd[0] = kr;
+                kd[1] = ki;
+                kd += ks;
                 const double nr = kr * lr - ki * li;
                 ki = kr * li + ki * lr;
                 kr = nr;
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < RM; ++r) {
+                if (r < R) {
+                    if (is_mu) {
+                        kmu[(r * NS + q) * 2 + 0] = kr;
+                        kmu[(r * NS + q) * 2 + 1] = ki;
+                    } else {
+                        knu[(r * NM + q) * 2 + 0] = kr;
+                        knu[(r * NM + q) * 2 + 1] = ki;
+                    }
+                    const double nr = kr * lr - ki * li;
+                    ki = kr * li + ki * lr;
+                    kr = nr;
+                }
             }
         }
     }
 }
 
 // nh is 16, 24 or 32 (spec::build_zpn)
-template <int NM, int NS, int RM, bool ZP>
+template <int NM, int NS, int RM, bool ZP, bool ENDS>
 __device__ __forceinline__ void zpn_fit_kappa(int tt, int nh, int R, const double *fitbuf, const double *mtab,
                                               const double *l256, double *kmu, double *knu) {
-    if (nh == 24) zpn_fit_kappa_n<NM, NS, 3, RM, ZP>(tt, R, fitbuf, mtab, l256, kmu, knu);
-    else if (nh == 32) zpn_fit_kappa_n<NM, NS, 4, RM, ZP>(tt, R, fitbuf, mtab, l256, kmu, knu);
-    else zpn_fit_kappa_n<NM, NS, 2, RM, ZP>(tt, R, fitbuf, mtab, l256, kmu, knu);
+    if (nh == 24) zpn_fit_kappa_n<NM, NS, 3, RM, ZP, ENDS>(tt, R, fitbuf, mtab, l256, kmu, knu);
+    else if (nh == 32) zpn_fit_kappa_n<NM, NS, 4, RM, ZP, ENDS>(tt, R, fitbuf, mtab, l256, kmu, knu);
+    else zpn_fit_kappa_n<NM, NS, 2, RM, ZP, ENDS>(tt, R, fitbuf, mtab, l256, kmu, knu);
 }
 
 // lambda_q^e, q = q0 .. q0 + NG - 1, e = 0..255, from the three-level table [20][NM][2]
@@ -192,6 +209,54 @@ __device__ __forceinline__ void zpn_bwd_bursts(double *im, double *c7, const dou
     }
 }
 
+// The forward bursts (Rf rows, 1 .. kSpecRMax of them, the NS slow modes): this block's mu leaves
+// row r, the previous block's arrives in row D + r (both rows live in re[]: D + r <= 8 + 4).
+// Rf is uniform: the rows are straight-line code that the first r >= Rf leaves, every row updated
+// in its own registers.  (A switch over row counts, one specialised copy each, hands all of re[]
+// through its join: sixteen register pairs copied per block, profiles/zpn_epilogue_counts.txt.)
+template <int D, int NS>
+__device__ __forceinline__ void zpn_fwd_bursts_to(int Rf, double *re, const double *kmu, const double *kpm,
+                                                  const double *Pr, const double *Pi, double &first) {
+#pragma unroll
+    for (int r = 0; r < kSpecRMax; ++r) {
+        if (r >= Rf) break;
+        double ca, cp;
+        zpn_dot2<NS>(kmu + (r * NS) * 2, kpm + (r * NS) * 2, Pr, Pi, ca, cp);
+        re[r] += ca;
+        re[D + r] += cp;
+        if (r == 0) first = ca;
+    }
+}
+
+// The backward bursts (R rows, 1 .. RM of them): this block's nu leaves window row 31 - r
+// (im[15 - r]) and arrives, with the same values, in the rows the previous block holds back (c7:
+// rows behind the first R are left as they are, nobody reads them).  The slow modes in every
+// row; the fast ones (all at once: one more round of table reads, not one per pair) in the
+// first.  RES: the fast modes' powers come in Fr / Fi (the resident instances); otherwise they
+// are formed here, from ptab at exponent e.  Rows as in zpn_fwd_bursts_to: left at the first r >= R.
+template <int NM, int NS, int RM, bool RES>
+__device__ __forceinline__ void zpn_bwd_bursts_to(int R, double *im, double *c7, const double *knu,
+                                                  const double *ptab, int e, const double *Pr, const double *Pi,
+                                                  const double *Fr, const double *Fi) {
+#pragma unroll
+    for (int r = 0; r < RM; ++r) {
+        if (r >= R) break;
+        double nb = zp_dot<NS>(knu + (r * NM) * 2, Pr, Pi);
+        if (r == 0 && NM > NS) {
+            constexpr int NF = NM > NS ? NM - NS : 1;
+            if (RES) {
+                nb += zp_dot<NF>(knu + NS * 2, Fr, Fi);
+            } else {
+                double fr[NF], fi[NF];
+                zpn_powers<NM, NF>(ptab, NS, e, fr, fi);
+                nb += zp_dot<NF>(knu + NS * 2, fr, fi);
+            }
+        }
+        im[15 - r] += nb;
+        c7[r] = nb;
+    }
+}
+
 // Which instances keep their mode powers in registers for the whole launch.  The powers of a
 // thread -- lambda_q^t of the slow modes for the forward bursts, lambda_q^(255 - t) of every mode
 // for the backward ones -- are the same in every block; formed per block each of the NS + NM
@@ -204,6 +269,24 @@ __device__ __forceinline__ void zpn_bwd_bursts(double *im, double *c7, const dou
 // rows on (the lower blocks carry more tail rows across, eight modes two more fast powers).
 template <int NB, int NM, int NS, int RM, bool ZP>
 constexpr bool zpn_resident = RM == kSpecRMax && NS == 2 && (!ZP || NM <= 4 || (NM == 6 && NB >= 27));
+
+// Which instances take the epilogue's rows -- of the fit, the bursts, the held rows and the row
+// stores -- as straight-line code that the first row the launch does not have leaves
+// (zpn_fwd_bursts_to), and which keep one specialised copy per row count behind a switch and
+// `r < R` around every row.  The first form executes less: nothing is handed through a join, no
+// row asks a flag the loop keeps in spilled scalar registers (profiles/zpn_epilogue_counts.txt:
+// 111 of 1851 vector instructions per wave and block in <27, 6, 2, 5, true>).  It also keeps a
+// row's amplitudes and sums alive beside the next row's, and where registers are short already --
+// powers formed per block, four slow modes and more, eight and twelve burst rows -- that spills.
+// Settled per instance from the compiler's report, as zpn_resident is
+// (profiles/zpn_epilogue_resources.txt: no more spills, no more scratch, two workgroups per CU):
+// the forward chain; of the zero-phase instances with five burst rows those of two modes, of four
+// (with two slow ones from 25 rows on) and of six with two slow ones from 27 rows on; of those with
+// eight burst rows the ones of two modes.  Every other instance compiles to the code it had.
+template <int NB, int NM, int NS, int RM, bool ZP>
+constexpr bool zpn_rows_end =
+    !ZP || (NM == 2 && RM <= 8) ||
+    (RM == kSpecRMax && ((NM == 4 && (NS == 4 || NB >= 25)) || (NM == 6 && NS == 2 && NB >= 27)));
 
 // RM: burst rows the instance holds registers for (5, or 8 for the long left tails of blocks of
 // 24 ... 26 rows).  ZP = false: the FORWARD chain (FIR -> sosfilt, chain_spec.hip's
@@ -279,6 +362,7 @@ __global__ __launch_bounds__(256, 2) void chain_zpn_kernel(ZpArgs g) {
     // the resident instances' mode powers, once per launch (the tables are in LDS now): lambda^t of
     // the slow modes, lambda^(255 - t) of the slow and of the fast ones
     constexpr bool RES = zpn_resident<NB, NM, NS, RM, ZP>;
+    constexpr bool ENDS = zpn_rows_end<NB, NM, NS, RM, ZP>;
     constexpr int NF = NM > NS ? NM - NS : 1;
     double rPr[NS], rPi[NS], rQr[NS], rQi[NS], rFr[NF], rFi[NF];
     if (RES) {
@@ -334,6 +418,11 @@ __global__ __launch_bounds__(256, 2) void chain_zpn_kernel(ZpArgs g) {
         int tt = t;
         asm volatile("" : "+v"(tt));
         const unsigned lane8 = 8u * (unsigned)tt;
+        // the row counts, as this block sees them: every `r < R` below is one scalar compare where
+        // it stands.  Known to be the launch's, the compares move out of the loop, each into a pair
+        // of scalar registers the loop has not got: two lane reads per use.
+        int Rb = R, Rfb = Rf, Rtb = Rt;
+        if (ENDS) asm volatile("" : "+s"(Rb), "+s"(Rfb), "+s"(Rtb));
         if (tt < nh) fitbuf[tt] = im[15];
         else if (tt >= 256 - nh) fitbuf[tt - 256 + ns] = im[15];
 #pragma unroll
@@ -341,30 +430,34 @@ __global__ __launch_bounds__(256, 2) void chain_zpn_kernel(ZpArgs g) {
         __syncthreads();
         // (this block's mu where the next block will look for the previous one's)
         double *kmu = kapP + (par ^ 1) * (Rt * NS * 2);
-        zpn_fit_kappa<NM, NS, RM, ZP>(tt, nh, Rt, fitbuf, mtab, lrow, kmu, knu);
+        zpn_fit_kappa<NM, NS, RM, ZP, ENDS>(tt, nh, Rtb, fitbuf, mtab, lrow, kmu, knu);
         __syncthreads();
-        double c7[RM];
+        double c7[RM];           // (rows r < R: written by the backward bursts, read nowhere else)
+        if (!ENDS) {
 #pragma unroll
-        for (int r = 0; r < RM; ++r) c7[r] = 0.0;
+            for (int r = 0; r < RM; ++r) c7[r] = 0.0;
+        }
         {
             double bPr[NS], bPi[NS];
             if (!RES) zpn_powers<NM, NS>(ptab, 0, tt, bPr, bPi);
             const double *Pr = RES ? rPr : bPr, *Pi = RES ? rPi : bPi;
             const double *kpm = kapP + par * (Rt * NS * 2);
             double ca = 0.0;
-            switch (Rf) {
+            if (ENDS) zpn_fwd_bursts_to<D, NS>(Rfb, re, kmu, kpm, Pr, Pi, ca);   // (1 <= Rf <= 5: the tables)
+            else switch (Rf) {
                 case 1: zpn_fwd_bursts<D, NS, 1>(re, kmu, kpm, Pr, Pi, ca); break;
                 case 2: zpn_fwd_bursts<D, NS, 2>(re, kmu, kpm, Pr, Pi, ca); break;
                 case 3: zpn_fwd_bursts<D, NS, 3>(re, kmu, kpm, Pr, Pi, ca); break;
                 case 4: zpn_fwd_bursts<D, NS, 4>(re, kmu, kpm, Pr, Pi, ca); break;
-                default: zpn_fwd_bursts<D, NS, 5>(re, kmu, kpm, Pr, Pi, ca); break;   // (Rf <= 5: the tables)
+                default: zpn_fwd_bursts<D, NS, 5>(re, kmu, kpm, Pr, Pi, ca); break;
             }
             // (no fence between the two halves: with two slow modes both sets of powers fit beside
             // the data, and the backward half's table reads go out behind the forward half's)
             double bQr[NS], bQi[NS];
             if (ZP && !RES) zpn_powers<NM, NS>(ptab, 0, 255 - tt, bQr, bQi);
             const double *Qr = RES ? rQr : bQr, *Qi = RES ? rQi : bQi;
-            if (ZP) switch (R) {
+            if (ZP && ENDS) zpn_bwd_bursts_to<NM, NS, RM, RES>(Rb, im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi);
+            else if (ZP) switch (R) {
                 case 1: zpn_bwd_bursts<NM, NS, 1, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
                 case 2: zpn_bwd_bursts<NM, NS, 2, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
                 case 3: zpn_bwd_bursts<NM, NS, 3, RES>(im, c7, knu, ptab, 255 - tt, Qr, Qi, rFr, rFi); break;
@@ -421,8 +514,10 @@ __global__ __launch_bounds__(256, 2) void chain_zpn_kernel(ZpArgs g) {
             if (!bad && !closing && o - S + L >= n0) {
                 const __amdgpu_buffer_rsrc_t ry = buf_rsrc(yr + (o - S + L));
 #pragma unroll
-                for (int r = 0; r < RM; ++r)
-                    if (r < R) buf_store(held[r] + c7[r], ry, lane8, 2048u * (NB - 1 - r));
+                for (int r = 0; r < RM; ++r) {
+                    if (ENDS && r >= Rb) break;
+                    if (ENDS || r < R) buf_store(held[r] + c7[r], ry, lane8, 2048u * (NB - 1 - r));
+                }
                 if (nst >= 0) nst += R;
             } else {
                 nst = -1;
@@ -465,10 +560,25 @@ __global__ __launch_bounds__(256, 2) void chain_zpn_kernel(ZpArgs g) {
                 if (!bad && !edge && o + L >= n0) {
                     // the common case: whole rows into the current output
                     const __amdgpu_buffer_rsrc_t ry = buf_rsrc(yr + (o + L));
+                    if (ENDS) {
+                        // (rows 0 .. NB - R - 1, the lower half first; R <= RM: only the last RM
+                        // of them ask, and the first that is held back ends the stores)
 #pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        if (RM <= NHI || j < NB - R) buf_store(re[j], ry, lane8, 2048u * j);   // (R <= RM <= NHI: every lower row)
-                        if (j < NHI - R) buf_store(im[j], ry, lane8, 2048u * (j + 16));
+                        for (int j = 0; j < 16; ++j) {
+                            if (j >= NB - RM && j >= NB - Rb) break;
+                            buf_store(re[j], ry, lane8, 2048u * j);
+                        }
+#pragma unroll
+                        for (int j = 0; j < NHI; ++j) {
+                            if (j >= NHI - RM && j >= NHI - Rb) break;
+                            buf_store(im[j], ry, lane8, 2048u * (j + 16));
+                        }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 16; ++j) {
+                            if (RM <= NHI || j < NB - R) buf_store(re[j], ry, lane8, 2048u * j);   // (R <= RM <= NHI: every lower row)
+                            if (j < NHI - R) buf_store(im[j], ry, lane8, 2048u * (j + 16));
+                        }
                     }
                     if (nst >= 0) nst += NB - R;
                 } else {
@@ -483,10 +593,11 @@ __global__ __launch_bounds__(256, 2) void chain_zpn_kernel(ZpArgs g) {
                 }
             }
             // (row NB - 1 - r: in the window's upper half as long as r < NHI, below it for the long
-            // left tails of blocks of 20 ... 23 rows)
+            // left tails of blocks of 20 ... 23 rows; all RM of them, read or not: a copy is one
+            // move, `r < R` makes it two selects)
 #pragma unroll
             for (int r = 0; r < RM; ++r)
-                if (r < R) held[r] = r < NHI ? im[(NHI - 1 - r) & 15] : re[(NB - 1 - r) & 15];
+                if (ENDS || r < R) held[r] = r < NHI ? im[(NHI - 1 - r) & 15] : re[(NB - 1 - r) & 15];
 #pragma unroll
             for (int j = 0; j < D; ++j) cr[j] = im[NHI + j];
         }
