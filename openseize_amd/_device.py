@@ -1677,6 +1677,29 @@ def spectral_features(P, k0, k1, df, bands, edges, normalize, mask, out, win0=0)
     return nseg
 
 
+def _pair_open(who, x2d, winsize, step, mask, tail, ok, told, planes, out, complex_too=False):
+    """``(lib, nch, n, nwin, pitch, work)`` for ``who``, a channel-pair window wrapper: the library,
+    the shape of the rows ``x2d``, the windows they hold, the pitch of the rows as the kernel takes
+    it and the work space that ``osz_<who>_work(nch, n, winsize, step, *tail)`` asks for (None
+    without a window).  ``who``'s ValueError for rows of another kind, for sizes or measures the
+    library refuses or a parameter of ``who``'s own that is not ``ok`` (``told``: those parameters,
+    as the message lists them) and, unless ``planes`` is None, for an ``out`` that is not a
+    contiguous float64 (planes, nwin, nch, nch) tensor on the device of the data."""
+    lib = require_gpu()
+    nch, n = _window_rows(who, x2d, complex_too)
+    need = getattr(lib, f"osz_{who}_work")(nch, n, int(winsize), int(step), *tail)
+    if need < 0 or not ok:
+        raise ValueError(f"{who}: bad sizes or measures{f' for {x2d.dtype} data' if complex_too else ''} "
+                         f"({nch}, {n}, {winsize}, {step}, {told}, {mask})")
+    nwin = lib.osz_window_count(n, int(winsize), int(step))
+    if planes is not None and (out.dtype != torch.float64 or tuple(out.shape) != (planes, nwin, nch, nch)
+                               or not out.is_contiguous() or out.device != x2d.device):
+        raise ValueError(f"{who}: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nwin}, {nch}, "
+                         f"{nch}) on the device of the data")
+    work = torch.empty(max(need, 1), dtype=torch.float64, device=x2d.device) if nwin else None
+    return lib, nch, n, nwin, max(x2d.stride(0), n), work
+
+
 def window_pairs(x2d, winsize, step, ddof, mask, out):
     """osz_window_pairs: the measures in the bit mask ``mask`` of every window of ``winsize``
     samples, ``step`` apart, that x2d -- (nch, n) float64 (cov, corr) or complex128 (aec, plv,
@@ -1684,22 +1707,12 @@ def window_pairs(x2d, winsize, step, ddof, mask, out):
     float64 (planes, nwin, nch, nch) CUDA tensor, one plane per measure present in the order of
     _lib.WINDOW_CONNECTIVITY.  The work space is allocated here and freed on return.  Returns the
     number of windows written."""
-    lib = require_gpu()
-    nch, n = _window_rows("window_pairs", x2d, complex_too=True)
     cplx = x2d.dtype == torch.complex128
-    need = lib.osz_window_pairs_work(nch, n, int(winsize), int(step), int(mask), int(cplx))
-    if need < 0 or ddof not in (0, 1):
-        raise ValueError(f"window_pairs: bad sizes or measures for {x2d.dtype} data ({nch}, {n}, {winsize}, {step}, "
-                         f"{ddof}, {mask})")
-    nwin = lib.osz_window_count(n, int(winsize), int(step))
-    planes = bin(int(mask)).count("1")
-    if (out.dtype != torch.float64 or tuple(out.shape) != (planes, nwin, nch, nch) or not out.is_contiguous()):
-        raise ValueError(f"window_pairs: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nwin}, {nch}, "
-                         f"{nch})")
+    lib, nch, n, nwin, pitch, work = _pair_open("window_pairs", x2d, winsize, step, mask, (int(mask), int(cplx)),
+                                                ddof in (0, 1), ddof, bin(int(mask)).count("1"), out, complex_too=True)
     if nwin:
-        work = torch.empty(max(need, 1), dtype=torch.float64, device=x2d.device)
-        _lib.check(lib.osz_window_pairs(ptr(x2d), max(x2d.stride(0), n), nch, n, int(cplx), int(winsize), int(step),
-                                        int(ddof), int(mask), ptr(out), out.stride(0), ptr(work), need, stream_ptr()))
+        _lib.check(lib.osz_window_pairs(ptr(x2d), pitch, nch, n, int(cplx), int(winsize), int(step), int(ddof),
+                                        int(mask), ptr(out), out.stride(0), ptr(work), work.numel(), stream_ptr()))
     return nwin
 
 
@@ -1711,13 +1724,8 @@ def window_xcorr(x2d, winsize, step, maxlag, normalize, mask, xcorr, out):
     ``out``: a contiguous float64 (planes, nwin, nch, nch) CUDA tensor, one plane per measure of peak,
     lag and signed present, in that order, else None.  The work space is allocated here and freed on
     return.  Returns the number of windows written."""
-    lib = require_gpu()
-    nch, n = _window_rows("window_xcorr", x2d)
-    need = lib.osz_window_xcorr_work(nch, n, int(winsize), int(step), int(maxlag), int(mask))
-    if need < 0 or not isinstance(normalize, bool):
-        raise ValueError(f"window_xcorr: bad sizes or measures ({nch}, {n}, {winsize}, {step}, {maxlag}, "
-                         f"{normalize!r}, {mask})")
-    nwin = lib.osz_window_count(n, int(winsize), int(step))
+    lib, nch, n, nwin, pitch, work = _pair_open("window_xcorr", x2d, winsize, step, mask, (int(maxlag), int(mask)),
+                                                isinstance(normalize, bool), f"{maxlag}, {normalize!r}", None, None)
     lags = 2 * int(maxlag) + 1
     planes = bin(int(mask) >> 1).count("1")
     want = ((xcorr, (nwin, lags, nch, nch), mask & 1), (out, (planes, nwin, nch, nch), planes))
@@ -1728,11 +1736,10 @@ def window_xcorr(x2d, winsize, step, maxlag, normalize, mask, xcorr, out):
                              f"{[s if a else None for _, s, a in want]}, got "
                              f"{[None if a is None else tuple(a.shape) for a, _, _ in want]}")
     if nwin:
-        work = torch.empty(max(need, 1), dtype=torch.float64, device=x2d.device)
-        _lib.check(lib.osz_window_xcorr(ptr(x2d), max(x2d.stride(0), n), nch, n, int(winsize), int(step), int(maxlag),
+        _lib.check(lib.osz_window_xcorr(ptr(x2d), pitch, nch, n, int(winsize), int(step), int(maxlag),
                                         int(normalize), int(mask), ptr(xcorr) if mask & 1 else None,
-                                        ptr(out) if planes else None, out.stride(0) if planes else 0, ptr(work), need,
-                                        stream_ptr()))
+                                        ptr(out) if planes else None, out.stride(0) if planes else 0, ptr(work),
+                                        work.numel(), stream_ptr()))
     return nwin
 
 
@@ -1743,19 +1750,9 @@ def window_granger(x2d, winsize, step, order, mask, out):
     out[p, k, i, j] (row the source, column the target): out a contiguous float64 (planes, nwin, nch,
     nch) CUDA tensor, one plane per measure present in the order of _lib.WINDOW_GRANGER.  The work
     space is allocated here and freed on return.  Returns the number of windows written."""
-    lib = require_gpu()
-    nch, n = _window_rows("window_granger", x2d)
-    need = lib.osz_window_granger_work(nch, n, int(winsize), int(step), int(order), int(mask))
-    if need < 0:
-        raise ValueError(f"window_granger: bad sizes or measures ({nch}, {n}, {winsize}, {step}, {order}, {mask})")
-    nwin = lib.osz_window_count(n, int(winsize), int(step))
-    planes = bin(int(mask)).count("1")
-    if (out.dtype != torch.float64 or tuple(out.shape) != (planes, nwin, nch, nch) or not out.is_contiguous()
-            or out.device != x2d.device):
-        raise ValueError(f"window_granger: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nwin}, {nch}, "
-                         f"{nch}) on the device of the data")
+    lib, nch, n, nwin, pitch, work = _pair_open("window_granger", x2d, winsize, step, mask, (int(order), int(mask)),
+                                                True, order, bin(int(mask)).count("1"), out)
     if nwin:
-        work = torch.empty(max(need, 1), dtype=torch.float64, device=x2d.device)
-        _lib.check(lib.osz_window_granger(ptr(x2d), max(x2d.stride(0), n), nch, n, int(winsize), int(step), int(order),
-                                          int(mask), ptr(out), out.stride(0), ptr(work), need, stream_ptr()))
+        _lib.check(lib.osz_window_granger(ptr(x2d), pitch, nch, n, int(winsize), int(step), int(order),
+                                          int(mask), ptr(out), out.stride(0), ptr(work), work.numel(), stream_ptr()))
     return nwin

@@ -8,16 +8,15 @@
 // Yule-Walker models of d_i and d_j alone, of the same order, with errors E_i and E_j:
 //   granger[i, j] = F_{i->j} = ln(E_j / S_jj),  instant = ln(S_ii S_jj / det S),
 //   total = (granger[i, j] + granger[j, i]) + instant.
-// Three steps: (1) K23's sums and lagged Gram kernels with L = p (wx_lagged_gram) write the upper
-// triangle of G(l) = W r(l), l = -p .. p, per window of a batch; (2) granger_auto_kernel, a thread per
-// (window, channel), runs Levinson's recursion on G_cc(0 .. p) / W and writes E_c; (3)
-// granger_pair_kernel, a lane per pair i < j, runs the block Levinson recursion (Whittle 1963;
-// Wiggins and Robinson 1965) with 2 x 2 blocks, the coefficient blocks in LDS, and writes both
-// mirrors.  DESIGN.md section 4, K24.
+// Three steps: (1) K23's sums and lagged Gram kernels with L = p (wx_window_sums, wx_lagged_gram)
+// write the upper triangle of G(l) = W r(l), l = -p .. p, per window of a batch; (2)
+// granger_auto_kernel, a thread per (window, channel), runs Levinson's recursion on G_cc(0 .. p) / W
+// and writes E_c; (3) granger_pair_kernel, a lane per pair i < j, runs the block Levinson recursion
+// (Whittle 1963; Wiggins and Robinson 1965) with 2 x 2 blocks, the coefficient blocks in LDS, and
+// writes both mirrors.  DESIGN.md section 4, K24.
 //
 // The order of every operation is a function of p alone and nothing is atomic.
-#include "pair_tile.h"
-#include "windowxcorr.h"
+#include "pair_window.h"
 
 namespace osz {
 
@@ -196,30 +195,16 @@ granger_pair_kernel(const double *__restrict__ part, const double *__restrict__ 
     for (int q = 0; q < OSZ_WG_COUNT; ++q) {
         if (!(mask & (1 << q))) continue;                    // (the same for the whole grid)
         if (mine || diag) o[plane * out_plane + at] = vals[q];
-        turn[a][b] = back[q];
-        __syncthreads();
-        if (mirrored) o[plane * out_plane + mirror] = turn[b][a];
-        __syncthreads();
+        pw_mirror(turn, a, b, back[q], mirrored, o + plane * out_plane + mirror);
         ++plane;
     }
 }
 
-struct WgPlan {
-    int64_t nwin, chan, one, batch, gram;                    // counts of doubles but nwin and batch
-};
-
 // The work space of one push: [chan: nch nwin] [E: nch nwin] [G: batch (2 p + 1) nch nch]
-static bool wg_plan(int nch, int64_t n, int64_t W, int64_t step, int p, int mask, WgPlan *q) {
-    if (nch < 2 || nch > 16384 || n < 0 || W < 16 || W > OSZ_WG_LONGEST || step < 1) return false;
-    if (p < 1 || p > OSZ_WG_MAXORDER || p > W / 8 || mask < 1 || mask >= 1 << OSZ_WG_COUNT) return false;
-    if ((int64_t)nch * n >= ((int64_t)1 << 40)) return false;
-    q->nwin = n < W ? 0 : (n - W) / step + 1;
-    q->chan = (int64_t)nch * q->nwin;
-    q->one = (int64_t)(2 * p + 1) * nch * nch;
-    const int64_t batch = wx_batch(q->one);
-    q->batch = batch < q->nwin ? batch : q->nwin;
-    q->gram = q->batch * q->one;
-    return true;
+static bool wg_plan(const PwArgs &A, PwPlan *q) {
+    const int p = A.value;
+    if (p < 1 || p > OSZ_WG_MAXORDER || p > A.W / 8) return false;
+    return pw_plan(A, OSZ_WG_COUNT, 16, OSZ_WG_LONGEST, 2, 2 * p + 1, q);
 }
 
 }  // namespace osz
@@ -229,36 +214,25 @@ using namespace osz;
 extern "C" {
 
 int64_t osz_window_granger_work(int nch, int64_t n, int64_t winsize, int64_t step, int order, int mask) {
-    WgPlan q;
-    if (!wg_plan(nch, n, winsize, step, order, mask, &q)) return -1;
-    return 2 * q.chan + q.gram;
+    PwPlan q;
+    return wg_plan({"osz_window_granger", nch, n, winsize, step, mask, "order", order}, &q) ? q.work() : -1;
 }
 
 int osz_window_granger(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int order,
                        int mask, double *out, int64_t plane_pitch, double *work, int64_t work_len, void *stream) {
-    WgPlan q;
-    OSZ_REQUIRE(x && out && work, "osz_window_granger: null argument");
-    OSZ_REQUIRE(wg_plan(nch, n, winsize, step, order, mask, &q),
-                "osz_window_granger: bad sizes or measures (nch %d, n %lld, winsize %lld, step %lld, order %d, mask %d)",
-                nch, (long long)n, (long long)winsize, (long long)step, order, mask);
-    OSZ_REQUIRE(pitch >= n, "osz_window_granger: pitch %lld is less than n %lld", (long long)pitch, (long long)n);
-    OSZ_REQUIRE(plane_pitch >= q.nwin * nch * nch, "osz_window_granger: plane_pitch %lld holds fewer than %lld windows",
-                (long long)plane_pitch, (long long)q.nwin);
-    OSZ_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(work)) &
-                 7) == 0,
-                "osz_window_granger: float64 arrays must be 8-byte aligned");
-    OSZ_REQUIRE(work_len >= 2 * q.chan + q.gram,
-                "osz_window_granger: work holds %lld doubles, osz_window_granger_work asks for %lld",
-                (long long)work_len, (long long)(2 * q.chan + q.gram));
-    if (q.nwin == 0) return OSZ_OK;
-    OSZ_REQUIRE(q.nwin <= INT32_MAX, "osz_window_granger: too many windows in one push");
+    const PwArgs A{"osz_window_granger", nch, n, winsize, step, mask, "order", order};
+    PwPlan q;
+    const int rc = pw_head(A, wg_plan(A, &q), q, {{x, 8}, {out, 8}, {work, 8}}, pitch, true, plane_pitch, work_len);
+    if (rc != OSZ_OK || q.nwin == 0) return rc;
     hipStream_t st = as_stream(stream);
-    double *chan = work, *err = work + q.chan, *part = work + 2 * q.chan;
+    double *chan = work, *err = work + q.chan / 2, *part = work + q.chan;     // (q.chan: the sums and E)
     const int ntile = (nch + kWgTile - 1) / kWgTile;
     const double cnt = (double)winsize;
-    for (int64_t w0 = 0; w0 < q.nwin; w0 += q.batch) {
-        const int64_t count = q.nwin - w0 < q.batch ? q.nwin - w0 : q.batch;
-        const int rc = wx_lagged_gram(x, pitch, nch, winsize, step, order, w0, count, chan, part, "window_granger_gram", st);
+    return pw_batches(q, [&](int64_t w0, int64_t count) -> int {
+        // (the sums batch by batch: they bring the batch's samples in for the Gram kernel)
+        int rc = wx_window_sums(x, pitch, nch, winsize, step, w0, count, chan, "window_granger_prepare", st);
+        if (rc != OSZ_OK) return rc;
+        rc = wx_lagged_gram(x, pitch, nch, winsize, step, order, w0, count, chan, part, "window_granger_gram", st);
         if (rc != OSZ_OK) return rc;
         {
             KernelTimer timer("window_granger_auto", st);
@@ -278,8 +252,8 @@ int osz_window_granger(const double *x, int64_t pitch, int nch, int64_t n, int64
             hipLaunchKernelGGL(granger_pair_kernel<16>, grid, dim3(kWave), 0, st, part, err, nch, ntile, order, cnt, mask,
                                out, plane_pitch, w0);
         OSZ_HIP(hipGetLastError());
-    }
-    return OSZ_OK;
+        return OSZ_OK;
+    });
 }
 
 }  // extern "C"

@@ -16,21 +16,18 @@
 // Every sum has an order that is a function of W alone and nothing is atomic: an element of G is
 // the MFMA's k-ordered chain over its own two rows, one chain per sub-block counted from the
 // window's start; a row's sum is lane-strided and folded by wave_sum63.
-#include "pair_tile.h"
+#include "pair_window.h"
 
 namespace osz {
 
-typedef double wp_d4 __attribute__((ext_vector_type(4)));   // one lane's share of a 16 x 16 tile
-
 constexpr int kWpBlock = OSZ_WC_BLOCK;        // samples per sub-block of a window
-constexpr int kWpTile = 16;                   // rows per side of an MFMA tile
+constexpr int kWpTile = kPwTile;              // rows per side of an MFMA tile
 constexpr int kWpSide = 64;                   // rows per side of a workgroup's block of pairs
 constexpr int kWpThreads = 256;               // 2 x 2 waves, each 2 x 2 tiles
 constexpr int kWpPitch = kWave + 2;           // doubles per staged row: rows r and r + 1 are 2 (mod 32) apart,
                                               // so the 16 rows x 2 k of a half-wave's operand read cover 32
                                               // distinct 8-byte bank pairs
 constexpr int kWpLoads = 2 * kWpSide * kWave / kWpThreads;   // 32 staged values per thread and step
-constexpr int64_t kWpGramCap = (int64_t)1 << 25;             // doubles of G one batch of windows may hold (256 MiB)
 
 static_assert(kWpBlock % kWave == 0, "a sub-block is a whole number of 64-sample steps");
 
@@ -52,30 +49,11 @@ window_stage_kernel(const cx *__restrict__ z, int64_t ld, int nch, int64_t n, do
     stage[2 * plane + at] = v.y / a;
 }
 
-// One wave per (window, row): chan[(w * 2) * nch + c] = sum over the window of x - p, p the
-// window's first sample; with ux / uy (complex data) chan[(w * 2 + 1) * nch + c] = sum |u|^2, else
-// 0.  Lane l owns the samples l + 64 k in that order; wave_sum63 folds the lanes.
+// window_sums<2> (pair_window.h): the sums of x - p and of |u|^2 per (row, window)
 __global__ void __launch_bounds__(kWave)
 window_sums_kernel(const double *__restrict__ x, int64_t ld, int nch, int64_t W, int64_t step,
                    const double *__restrict__ ux, const double *__restrict__ uy, double *__restrict__ chan) {
-    const int64_t w = blockIdx.x;
-    const int c = blockIdx.y, lane = threadIdx.x;
-    const int64_t at = (int64_t)c * ld + w * step;
-    const double p = x[at];
-    double s = 0.0, f = 0.0;
-    for (int64_t t = lane; t < W; t += kWave) {
-        s += x[at + t] - p;
-        if (ux) {
-            const double a = ux[at + t], b = uy[at + t];
-            f += __builtin_fma(a, a, b * b);
-        }
-    }
-    s = wave_sum63(s);
-    f = wave_sum63(f);
-    if (lane == kWave - 1) {
-        chan[(w * 2) * nch + c] = s;
-        chan[(w * 2 + 1) * nch + c] = f;
-    }
+    window_sums<2>(x, ld, nch, W, step, ux, uy, chan);
 }
 
 // G = R R^T of one sub-block of one window over one 64 x 64 block of row pairs (block row bi <=
@@ -125,11 +103,11 @@ window_gram_kernel(const double *__restrict__ rows, int64_t ld, int nrows, int64
             const int i0 = bi * kWpSide + wi * 32 + a * kWpTile, j0 = bj * kWpSide + wj * 32 + b * kWpTile;
             act[a][b] = i0 < nrows && j0 < nrows && i0 <= j0;
         }
-    wp_d4 acc[2][2];
+    pair_d4 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = wp_d4{0.0, 0.0, 0.0, 0.0};
+        for (int b = 0; b < 2; ++b) acc[a][b] = pair_d4{0.0, 0.0, 0.0, 0.0};
 
     const int ra = wi * 32 + (lane & 15), rb = (diag ? 0 : kWpSide) + wj * 32 + (lane & 15), kq = lane >> 4;
 #pragma unroll
@@ -263,25 +241,14 @@ window_finish_kernel(const double *__restrict__ part, int nsub, const double *__
     }
 }
 
-struct WpPlan {
-    int64_t nwin, nsub, stage, chan, batch, gram;            // counts of doubles but nwin, nsub, batch
-};
-
 // The work space of one push: [stage: 3 nch n (complex)] [chan: 2 nch nwin] [G: batch nsub R R]
-static bool wp_plan(int nch, int64_t n, int64_t W, int64_t step, int mask, int is_complex, WpPlan *p) {
-    if (nch < 2 || nch > 16384 || n < 0 || W < 4 || step < 1 || mask < 1 || mask >= 1 << OSZ_WC_COUNT) return false;
-    if (wp_complex_mask(mask) != (is_complex != 0) || (is_complex && (mask & 3))) return false;
-    if ((int64_t)nch * n >= ((int64_t)1 << 40)) return false;
-    p->nwin = n < W ? 0 : (n - W) / step + 1;
-    p->nsub = (W + kWpBlock - 1) / kWpBlock;
+static bool wp_plan(const PwArgs &A, PwPlan *p) {
+    const bool is_complex = A.value != 0;
+    if (wp_complex_mask(A.mask) != is_complex || (is_complex && (A.mask & 3))) return false;
+    p->nsub = (A.W + kWpBlock - 1) / kWpBlock;
     if (p->nsub > 65535) return false;
-    const int64_t rows = wp_lock(mask) ? 2 * (int64_t)nch : nch, one = p->nsub * rows * rows;
-    p->stage = is_complex ? 3 * (int64_t)nch * n : 0;
-    p->chan = 2 * (int64_t)nch * p->nwin;
-    int64_t batch = kWpGramCap / one;
-    batch = batch < 1 ? 1 : batch > 65535 ? 65535 : batch;
-    p->batch = batch < p->nwin ? batch : p->nwin;
-    p->gram = p->batch * one;
+    if (!pw_plan(A, OSZ_WC_COUNT, 4, kAnyLength, 2, p->nsub * (wp_lock(A.mask) ? 4 : 1), p)) return false;
+    p->stage = is_complex ? 3 * (int64_t)A.nch * A.n : 0;
     return true;
 }
 
@@ -300,31 +267,19 @@ using namespace osz;
 extern "C" {
 
 int64_t osz_window_pairs_work(int nch, int64_t n, int64_t winsize, int64_t step, int mask, int is_complex) {
-    WpPlan p;
-    if (!wp_plan(nch, n, winsize, step, mask, is_complex, &p)) return -1;
-    return p.stage + p.chan + p.gram;
+    PwPlan p;
+    return wp_plan({"osz_window_pairs", nch, n, winsize, step, mask, "complex", is_complex}, &p) ? p.work() : -1;
 }
 
 int osz_window_pairs(const void *x, int64_t pitch, int nch, int64_t n, int is_complex, int64_t winsize, int64_t step,
                      int ddof, int mask, double *out, int64_t plane_pitch, double *work, int64_t work_len,
                      void *stream) {
-    WpPlan p;
-    OSZ_REQUIRE(x && out && work, "osz_window_pairs: null argument");
-    OSZ_REQUIRE(wp_plan(nch, n, winsize, step, mask, is_complex, &p),
-                "osz_window_pairs: bad sizes or measures (nch %d, n %lld, winsize %lld, step %lld, mask %d, complex %d)",
-                nch, (long long)n, (long long)winsize, (long long)step, mask, is_complex);
-    OSZ_REQUIRE(ddof == 0 || ddof == 1, "osz_window_pairs: ddof must be 0 or 1, got %d", ddof);
-    OSZ_REQUIRE(pitch >= n, "osz_window_pairs: pitch %lld is less than n %lld", (long long)pitch, (long long)n);
-    OSZ_REQUIRE(plane_pitch >= p.nwin * nch * nch, "osz_window_pairs: plane_pitch %lld holds fewer than %lld windows",
-                (long long)plane_pitch, (long long)p.nwin);
-    OSZ_REQUIRE((reinterpret_cast<uintptr_t>(x) & (is_complex ? 15 : 7)) == 0 &&
-                    ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(work)) & 7) == 0,
-                "osz_window_pairs: complex data must be 16-byte aligned, float64 arrays 8-byte aligned");
-    OSZ_REQUIRE(work_len >= p.stage + p.chan + p.gram,
-                "osz_window_pairs: work holds %lld doubles, osz_window_pairs_work asks for %lld", (long long)work_len,
-                (long long)(p.stage + p.chan + p.gram));
+    const PwArgs A{"osz_window_pairs", nch, n, winsize, step, mask, "complex", is_complex, "ddof", ddof};
+    PwPlan p;
+    const int rc = pw_head(A, wp_plan(A, &p), p, {{x, is_complex ? 16u : 8u}, {out, 8}, {work, 8}}, pitch, true,
+                           plane_pitch, work_len);
+    if (rc != OSZ_OK) return rc;
     if (p.nwin == 0) return OSZ_OK;
-    OSZ_REQUIRE(p.nwin <= INT32_MAX, "osz_window_pairs: too many windows in one push");
     hipStream_t st = as_stream(stream);
     double *stage = work, *chan = work + p.stage, *part = chan + p.chan;
     const int64_t plane = (int64_t)nch * n, cc = (int64_t)nch * nch;
@@ -343,8 +298,7 @@ int osz_window_pairs(const void *x, int64_t pitch, int nch, int64_t n, int is_co
     const dim3 fgrid((unsigned)((cc + 255) / 256), 1);
     const double cnt = (double)winsize, div = (double)(winsize - ddof);
     const int pivoted = mask & ((1 << OSZ_WC_COV) | (1 << OSZ_WC_CORR) | (1 << OSZ_WC_AEC));
-    for (int64_t w0 = 0; w0 < p.nwin; w0 += p.batch) {
-        const int64_t count = p.nwin - w0 < p.batch ? p.nwin - w0 : p.batch;
+    return pw_batches(p, [&](int64_t w0, int64_t count) -> int {
         dim3 grid = fgrid;
         grid.y = (unsigned)count;
         if (pivoted) {
@@ -366,8 +320,8 @@ int osz_window_pairs(const void *x, int64_t pitch, int nch, int64_t n, int is_co
                                mask, out, plane_pitch, w0);
         }
         OSZ_HIP(hipGetLastError());
-    }
-    return OSZ_OK;
+        return OSZ_OK;
+    });
 }
 
 }  // extern "C"

@@ -14,14 +14,11 @@
 // G(l) is the MFMA's k-ordered chain over t = 0 .. W - 1 in quads counted from the window's start
 // (a factor outside the window is a staged +0.0), whichever lags share its workgroup; a row's sum
 // is lane-strided and folded by wave_sum63.
-#include "pair_tile.h"
-#include "windowxcorr.h"
+#include "pair_window.h"
 
 namespace osz {
 
-typedef double wx_d4 __attribute__((ext_vector_type(4)));   // one lane's share of a 16 x 16 tile
-
-constexpr int kWxTile = 16;                   // rows per side of an MFMA tile
+constexpr int kWxTile = kPwTile;              // rows per side of an MFMA tile
 constexpr int kWxSide = 32;                   // rows per side of a workgroup's block of pairs: 2 x 2 tiles
 constexpr int kWxThreads = 256;               // 4 waves: each all 2 x 2 tiles of kWxLags lags
 constexpr int kWxLags = 4;                    // lags per wave: 16 accumulator tiles, 128 registers
@@ -31,24 +28,15 @@ constexpr int kWxPitchA = kWave + 2;          // doubles per staged row: 2 (mod 
 constexpr int kWxPitchB = kWave + 2 * kWxHalo + 2;   // 16 rows x 2 k of a half-wave's read cover 32 distinct
                                               // bank pairs; a lag shifts every lane alike and keeps that
 constexpr int kWxFinish = 16;                 // pairs per side of a finishing workgroup's tile
-constexpr int64_t kWxGramCap = (int64_t)1 << 25;     // doubles of G one batch of windows may hold (256 MiB)
 
 static_assert(kWxPitchA % 32 == 2 && kWxPitchB % 32 == 2, "the staging pitches are 2 (mod 32) doubles");
 static_assert(kWxSide % (kWxThreads / kWave) == 0, "the staged rows are dealt evenly to the waves");
 
-// One wave per (window, row): chan[w * nch + c] = sum over the window of x - p, p the window's
-// first sample.  Lane l owns the samples l + 64 k in that order; wave_sum63 folds the lanes.
+// window_sums<1> (pair_window.h): the sum of x - p per (row, window), chan[w * nch + c]
 __global__ void __launch_bounds__(kWave)
 xcorr_sums_kernel(const double *__restrict__ x, int64_t ld, int nch, int64_t W, int64_t step,
                   double *__restrict__ chan) {
-    const int64_t w = blockIdx.x;
-    const int c = blockIdx.y, lane = threadIdx.x;
-    const int64_t at = (int64_t)c * ld + w * step;
-    const double p = x[at];
-    double s = 0.0;
-    for (int64_t t = lane; t < W; t += kWave) s += x[at + t] - p;
-    s = wave_sum63(s);
-    if (lane == kWave - 1) chan[w * nch + c] = s;
+    window_sums<1>(x, ld, nch, W, step, nullptr, nullptr, chan);
 }
 
 // G(l) of one window over one 32 x 32 block of row pairs (block row bi <= block column bj) and
@@ -95,13 +83,13 @@ xcorr_gram_kernel(const double *__restrict__ rows, int64_t ld, int nrows, int W,
             const int i0 = bi * kWxSide + a * kWxTile, j0 = bj * kWxSide + b * kWxTile;
             act[a][b] = i0 < nrows && j0 < nrows && i0 <= j0;
         }
-    wx_d4 acc[2][2][kWxLags];
+    pair_d4 acc[2][2][kWxLags];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
-            for (int q = 0; q < kWxLags; ++q) acc[a][b][q] = wx_d4{0.0, 0.0, 0.0, 0.0};
+            for (int q = 0; q < kWxLags; ++q) acc[a][b][q] = pair_d4{0.0, 0.0, 0.0, 0.0};
     int shift[kWxLags];                                      // where lag q's B operand starts in a staged row
 #pragma unroll
     for (int q = 0; q < kWxLags; ++q) shift[q] = kWxHalo + min(m0 + q - L, L);
@@ -224,12 +212,7 @@ xcorr_finish_kernel(const double *__restrict__ part, int nch, int ntile, int L, 
                 sgn = v;
             }
         }
-        if (x) {
-            turn[a][b] = v;
-            __syncthreads();
-            if (mirrored) x[(L - l) * rr + mirror] = turn[b][a];
-            __syncthreads();
-        }
+        if (x) pw_mirror(turn, a, b, v, mirrored, x + (L - l) * rr + mirror);
     }
     double peak = lost ? nan : best, lag = lost ? nan : (double)bl;
     if (i == j) {
@@ -243,29 +226,27 @@ xcorr_finish_kernel(const double *__restrict__ part, int nch, int ntile, int L, 
     for (int m = 0; m < 3; ++m) {
         if (!(mask & (1 << (OSZ_WX_PEAK + m)))) continue;    // (the same for the whole grid)
         if (mine) o[plane * out_plane + at] = vals[m];
-        turn[a][b] = vals[m];
-        __syncthreads();
-        if (mirrored) o[plane * out_plane + mirror] = m == 1 ? 0.0 - turn[b][a] : turn[b][a];
-        __syncthreads();
+        pw_mirror(turn, a, b, m == 1 ? 0.0 - vals[m] : vals[m], mirrored, o + plane * out_plane + mirror);
         ++plane;
     }
 }
 
-// The windows whose G, `one` doubles a window, one batch holds: kWxGramCap doubles, a grid's y.
-int64_t wx_batch(int64_t one) {
-    const int64_t batch = kWxGramCap / one;
-    return batch < 1 ? 1 : batch > 65535 ? 65535 : batch;
+int wx_window_sums(const double *x, int64_t pitch, int nch, int64_t W, int64_t step, int64_t w0, int64_t count,
+                   double *chan, const char *timer, hipStream_t st) {
+    OSZ_REQUIRE(w0 >= 0 && count >= 1 && count <= INT32_MAX && nch >= 1 && nch <= 16384, "wx_window_sums: bad sizes");
+    KernelTimer t(timer, st);
+    hipLaunchKernelGGL(xcorr_sums_kernel, dim3((unsigned)count, (unsigned)nch), dim3(kWave), 0, st, x + w0 * step, pitch,
+                       nch, W, step, chan + w0 * nch);
+    OSZ_HIP(hipGetLastError());
+    return OSZ_OK;
 }
 
 int wx_lagged_gram(const double *x, int64_t pitch, int nch, int64_t W, int64_t step, int L, int64_t w0,
-                   int64_t count, double *chan, double *part, const char *timer, hipStream_t st) {
+                   int64_t count, const double *chan, double *part, const char *timer, hipStream_t st) {
     OSZ_REQUIRE(count >= 1 && count <= 65535 && L >= 0 && L <= OSZ_WX_MAXLAG && L <= W / 2 && nch >= 1 &&
                     nch <= 16384 && W <= OSZ_WX_LONGEST,
                 "wx_lagged_gram: bad sizes");
     const int nblk = (nch + kWxSide - 1) / kWxSide, ngroups = (2 * L + 1 + kWxGroup - 1) / kWxGroup;
-    hipLaunchKernelGGL(xcorr_sums_kernel, dim3((unsigned)count, (unsigned)nch), dim3(kWave), 0, st, x + w0 * step,
-                       pitch, nch, W, step, chan + w0 * nch);
-    OSZ_HIP(hipGetLastError());
     KernelTimer t(timer, st);
     hipLaunchKernelGGL(xcorr_gram_kernel, dim3((unsigned)(nblk * (nblk + 1) / 2), (unsigned)count, (unsigned)ngroups),
                        dim3(kWxThreads), 0, st, x, pitch, nch, (int)W, step, w0, nblk, L, chan, part);
@@ -273,22 +254,11 @@ int wx_lagged_gram(const double *x, int64_t pitch, int nch, int64_t W, int64_t s
     return OSZ_OK;
 }
 
-struct WxPlan {
-    int64_t nwin, chan, one, batch, gram;                    // counts of doubles but nwin and batch
-};
-
 // The work space of one push: [chan: nch nwin] [G: batch (2 L + 1) nch nch]
-static bool wx_plan(int nch, int64_t n, int64_t W, int64_t step, int L, int mask, WxPlan *p) {
-    if (nch < 2 || nch > 16384 || n < 0 || W < 8 || W > OSZ_WX_LONGEST || step < 1) return false;
-    if (L < 0 || L > OSZ_WX_MAXLAG || L > W / 2 || mask < 1 || mask >= 1 << OSZ_WX_COUNT) return false;
-    if ((int64_t)nch * n >= ((int64_t)1 << 40)) return false;
-    p->nwin = n < W ? 0 : (n - W) / step + 1;
-    p->chan = (int64_t)nch * p->nwin;
-    p->one = (int64_t)(2 * L + 1) * nch * nch;
-    const int64_t batch = wx_batch(p->one);
-    p->batch = batch < p->nwin ? batch : p->nwin;
-    p->gram = p->batch * p->one;
-    return true;
+static bool wx_plan(const PwArgs &A, PwPlan *p) {
+    const int L = A.value;
+    if (L < 0 || L > OSZ_WX_MAXLAG || L > A.W / 2) return false;
+    return pw_plan(A, OSZ_WX_COUNT, 8, OSZ_WX_LONGEST, 1, 2 * L + 1, p);
 }
 
 }  // namespace osz
@@ -298,59 +268,35 @@ using namespace osz;
 extern "C" {
 
 int64_t osz_window_xcorr_work(int nch, int64_t n, int64_t winsize, int64_t step, int maxlag, int mask) {
-    WxPlan p;
-    if (!wx_plan(nch, n, winsize, step, maxlag, mask, &p)) return -1;
-    return p.chan + p.gram;
+    PwPlan p;
+    return wx_plan({"osz_window_xcorr", nch, n, winsize, step, mask, "maxlag", maxlag}, &p) ? p.work() : -1;
 }
 
 int osz_window_xcorr(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int maxlag,
                      int normalize, int mask, double *xcorr, double *out, int64_t plane_pitch, double *work,
                      int64_t work_len, void *stream) {
-    WxPlan p;
-    OSZ_REQUIRE(x && work, "osz_window_xcorr: null argument");
-    OSZ_REQUIRE(wx_plan(nch, n, winsize, step, maxlag, mask, &p),
-                "osz_window_xcorr: bad sizes or measures (nch %d, n %lld, winsize %lld, step %lld, maxlag %d, mask %d)",
-                nch, (long long)n, (long long)winsize, (long long)step, maxlag, mask);
-    const int matrices = mask & ~(1 << OSZ_WX_XCORR);
-    OSZ_REQUIRE(normalize == 0 || normalize == 1, "osz_window_xcorr: normalize must be 0 or 1, got %d", normalize);
-    OSZ_REQUIRE((xcorr || !(mask & (1 << OSZ_WX_XCORR))) && (out || !matrices),
-                "osz_window_xcorr: mask %d needs an array that is null", mask);
-    OSZ_REQUIRE(pitch >= n, "osz_window_xcorr: pitch %lld is less than n %lld", (long long)pitch, (long long)n);
-    OSZ_REQUIRE(!matrices || plane_pitch >= p.nwin * nch * nch,
-                "osz_window_xcorr: plane_pitch %lld holds fewer than %lld windows", (long long)plane_pitch,
-                (long long)p.nwin);
-    OSZ_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(xcorr) | reinterpret_cast<uintptr_t>(out) |
-                  reinterpret_cast<uintptr_t>(work)) & 7) == 0,
-                "osz_window_xcorr: float64 arrays must be 8-byte aligned");
-    OSZ_REQUIRE(work_len >= p.chan + p.gram,
-                "osz_window_xcorr: work holds %lld doubles, osz_window_xcorr_work asks for %lld", (long long)work_len,
-                (long long)(p.chan + p.gram));
+    const PwArgs A{"osz_window_xcorr", nch, n, winsize, step, mask, "maxlag", maxlag, "normalize", normalize};
+    const bool full = mask & (1 << OSZ_WX_XCORR), matrices = mask & ~(1 << OSZ_WX_XCORR);
+    PwPlan p;
+    const int rc = pw_head(A, wx_plan(A, &p), p, {{x, 8}, {work, 8}, {xcorr, 8, true, full}, {out, 8, true, matrices}}, pitch,
+                           matrices, plane_pitch, work_len);
+    if (rc != OSZ_OK) return rc;
     if (p.nwin == 0) return OSZ_OK;
-    OSZ_REQUIRE(p.nwin <= INT32_MAX, "osz_window_xcorr: too many windows in one push");
     hipStream_t st = as_stream(stream);
     double *chan = work, *part = work + p.chan;
     const int ntile = (nch + kWxFinish - 1) / kWxFinish;
-    const int nblk = (nch + kWxSide - 1) / kWxSide, ngroups = (2 * maxlag + 1 + kWxGroup - 1) / kWxGroup;
-    {
-        KernelTimer timer("window_xcorr_prepare", st);
-        hipLaunchKernelGGL(xcorr_sums_kernel, dim3((unsigned)p.nwin, (unsigned)nch), dim3(kWave), 0, st, x, pitch, nch,
-                           winsize, step, chan);
-        OSZ_HIP(hipGetLastError());
-    }
-    for (int64_t w0 = 0; w0 < p.nwin; w0 += p.batch) {
-        const int64_t count = p.nwin - w0 < p.batch ? p.nwin - w0 : p.batch;
-        {
-            KernelTimer timer("window_xcorr_gram", st);
-            hipLaunchKernelGGL(xcorr_gram_kernel, dim3((unsigned)(nblk * (nblk + 1) / 2), (unsigned)count, (unsigned)ngroups),
-                               dim3(kWxThreads), 0, st, x, pitch, nch, (int)winsize, step, w0, nblk, maxlag, chan, part);
-        }
+    const int sums = wx_window_sums(x, pitch, nch, winsize, step, 0, p.nwin, chan, "window_xcorr_prepare", st);
+    if (sums != OSZ_OK) return sums;
+    return pw_batches(p, [&](int64_t w0, int64_t count) -> int {
+        const int rc = wx_lagged_gram(x, pitch, nch, winsize, step, maxlag, w0, count, chan, part, "window_xcorr_gram", st);
+        if (rc != OSZ_OK) return rc;
         KernelTimer timer("window_xcorr_finish", st);
         hipLaunchKernelGGL(xcorr_finish_kernel, dim3((unsigned)(ntile * (ntile + 1) / 2), (unsigned)count),
                            dim3(kWxFinish * kWxFinish), 0, st, part, nch, ntile, maxlag, (double)winsize, normalize, mask,
                            xcorr, out, plane_pitch, w0);
         OSZ_HIP(hipGetLastError());
-    }
-    return OSZ_OK;
+        return OSZ_OK;
+    });
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@ windows into launches, and the shaping of the planes into the result.  The kerne
 parameters and the names they take are each function's own, in its own module.
 """
 
+import functools
+
 import numpy as np
 
 from openseize_amd import _device as dev
@@ -158,6 +160,46 @@ def _planes(who, pro, W, step, kind, layout, count, launch):
         launch(x, out)
         parts.append(out.cpu().numpy() if host else out)
     return parts, host
+
+
+def _pair_planes(who, pro, W, step, kind, layout, rows, count, launch, advice="", lags=0):
+    """The launches of a channel-pair function that writes ``count`` (nch, nch) planes per window and,
+    with ``lags`` (window_xcorr's ``"xcorr"``), ``lags`` more in an array of their own: for every
+    ``(x, n, host)`` of ``_launches``, ``launch(x, out, more)`` fills ``out``, a float64 (count, n, nch,
+    nch) CUDA tensor allocated here (None for no plane), and ``more``, (n, lags, nch, nch) (None for
+    no lag); both go down to the host if ``host``.  Returns ``(planes, more)`` of the whole stream,
+    (count, nwin, nch, nch) and (nwin, lags, nch, nch).  CUDA-fed results stay on the device: when
+    they exceed the free device memory, MemoryError before the first launch, with ``advice`` on
+    ``who``'s own parameters."""
+    torch, nch = dev.torch, layout.nch
+    window_bytes = 8 * nch * nch * (count + lags)
+    empty = functools.partial(torch.empty, dtype=torch.float64)
+    parts, more = [], []
+    for x, n, host in _launches(who, pro, W, step, kind, rows, window_bytes):
+        if not parts and not more and not host:              # (before the first launch)
+            expect = window_count(pro.shape[layout.axis], W, step)
+            need, free = window_bytes * expect, torch.cuda.mem_get_info()[0]
+            if need > free:
+                raise MemoryError(f"{who}: the results of {expect} windows, {count} x ({nch}, {nch}) float64 each"
+                                  f"{f' and {lags} more for xcorr' if lags else ''}, need {need / 1e9:.2f} GB, more than "
+                                  f"the {free / 1e9:.2f} GB of device memory that are free: raise step (now {step}; "
+                                  f"winsize {W}){advice} or select fewer of the {nch} channels")
+        out = empty((count, n, nch, nch), device=x.device) if count else None
+        xc = empty((n, lags, nch, nch), device=x.device) if lags else None
+        launch(x, out, xc)
+        if count:
+            parts.append(out.cpu().numpy() if host else out)
+        if lags:
+            more.append(xc.cpu().numpy() if host else xc)
+
+    def whole(found, axis):
+        return None if not found else np.concatenate(found, axis=axis) if host else torch.cat(found, dim=axis)
+    return whole(parts, 1), whole(more, 0)
+
+
+def _asked(asked, names, found):
+    """``found[name]`` for one name ``asked``, else the dict of ``names`` in the order asked."""
+    return found[names[0]] if _is_one(asked) else {name: found[name] for name in names}
 
 
 def _result(parts, host, layout, asked, names, where):

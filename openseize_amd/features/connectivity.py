@@ -98,24 +98,9 @@ def window_connectivity(data, winsize, step=None, measures=("corr",), ddof=1, ax
         raise ValueError(f"window_connectivity: ddof must be 0 or 1, got {ddof!r}")
     kind = functools.partial(_kind, names)
     pro, layout = _stream._open(who, data, axis, chunksize, W, kind, pairs=True)
-    nch = layout.nch
     is_complex = names[0] not in _REAL
     order = [m for m in WINDOW_CONNECTIVITY if m in names]    # the planes a launch writes
     mask = dev.name_mask(_lib.WINDOW_CONNECTIVITY, order)
-    expect = window_count(pro.shape[layout.axis], W, step)
-    need = 8 * len(order) * nch * nch * expect
-    torch = dev.torch
-    parts, host = [], None
-    for x, n, host in _stream._launches(who, pro, W, step, kind, lambda arr: _rows(arr, layout, is_complex),
-                                        8 * len(order) * nch * nch):
-        if not parts and not host and need > torch.cuda.mem_get_info()[0]:      # (before the first launch)
-            raise MemoryError(f"window_connectivity: the {len(order)} x ({expect}, {nch}, "
-                              f"{nch}) float64 results need {need / 1e9:.2f} GB, more than the "
-                              f"{torch.cuda.mem_get_info()[0] / 1e9:.2f} GB of device memory that are free: "
-                              f"raise step (now {step}; winsize {W}) or select fewer of the {nch} channels")
-        out = torch.empty((len(order), n, nch, nch), dtype=torch.float64, device=x.device)
-        dev.window_pairs(x, W, step, ddof, mask, out)
-        parts.append(out.cpu().numpy() if host else out)
-    planes = np.concatenate(parts, axis=1) if host else torch.cat(parts, dim=1)
-    out = {name: planes[order.index(name)] for name in names}
-    return planes.shape[1], out[names[0]] if _stream._is_one(measures) else out
+    planes, _ = _stream._pair_planes(who, pro, W, step, kind, layout, lambda arr: _rows(arr, layout, is_complex),
+                                     len(order), lambda x, out, _: dev.window_pairs(x, W, step, ddof, mask, out))
+    return planes.shape[1], _stream._asked(measures, names, {name: planes[order.index(name)] for name in names})

@@ -7,12 +7,9 @@ Yule-Walker equations of every pair are solved by the block Levinson recursion:
 ``csrc/windowgranger.hip`` (K24), ``osz_window_granger``.
 """
 
-import numpy as np
-
 from openseize_amd import _device as dev
 from openseize_amd import _lib
 from openseize_amd.features import _stream
-from openseize_amd.features._stream import window_count
 
 WINDOW_GRANGER = tuple(_lib.WINDOW_GRANGER)
 
@@ -84,23 +81,8 @@ def window_granger(data, winsize, step=None, measures=("granger",), order=8, axi
         raise ValueError(f"window_granger: order must be at most winsize // 8 = {W // 8}, got {p}")
     kind = _stream._real_only(who)
     pro, layout = _stream._open(who, data, axis, chunksize, W, kind, pairs=True)
-    nch = layout.nch
     planes = [m for m in WINDOW_GRANGER if m in names]       # the (C, C) planes a launch writes
     mask = dev.name_mask(_lib.WINDOW_GRANGER, names)
-    window_bytes = 8 * nch * nch * len(planes)
-    expect = window_count(pro.shape[layout.axis], W, step)
-    need = window_bytes * expect
-    torch = dev.torch
-    parts, host = [], None
-    for x, n, host in _stream._launches(who, pro, W, step, kind, layout.to2d, window_bytes):
-        if not parts and not host and need > torch.cuda.mem_get_info()[0]:   # (before the first launch)
-            raise MemoryError(f"window_granger: the results of {expect} windows, {len(planes)} x ({nch}, {nch}) float64 "
-                              f"each, need {need / 1e9:.2f} GB, more than the "
-                              f"{torch.cuda.mem_get_info()[0] / 1e9:.2f} GB of device memory that are free: raise "
-                              f"step (now {step}; winsize {W}) or select fewer of the {nch} channels")
-        out = torch.empty((len(planes), n, nch, nch), dtype=torch.float64, device=x.device)
-        dev.window_granger(x, W, step, p, mask, out)
-        parts.append(out.cpu().numpy() if host else out)
-    whole = np.concatenate(parts, axis=1) if host else torch.cat(parts, dim=1)
-    out = {name: whole[planes.index(name)] for name in names}
-    return out[names[0]].shape[0], out[names[0]] if _stream._is_one(measures) else out
+    whole, _ = _stream._pair_planes(who, pro, W, step, kind, layout, layout.to2d, len(planes),
+                                    lambda x, out, _: dev.window_granger(x, W, step, p, mask, out))
+    return whole.shape[1], _stream._asked(measures, names, {name: whole[planes.index(name)] for name in names})

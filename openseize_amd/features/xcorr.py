@@ -12,7 +12,6 @@ import numpy as np
 from openseize_amd import _device as dev
 from openseize_amd import _lib
 from openseize_amd.features import _stream
-from openseize_amd.features._stream import window_count
 
 WINDOW_XCORR = tuple(_lib.WINDOW_XCORR)
 
@@ -98,36 +97,12 @@ def window_xcorr(data, winsize, step=None, measures=("peak", "lag"), maxlag=16, 
     normalize = bool(normalize)
     kind = _stream._real_only(who)
     pro, layout = _stream._open(who, data, axis, chunksize, W, kind, pairs=True)
-    nch = layout.nch
     order = [m for m in WINDOW_XCORR[1:] if m in names]       # the (C, C) planes a launch writes
-    full = "xcorr" in names
     mask = dev.name_mask(_lib.WINDOW_XCORR, names)
-    lags = 2 * L + 1
-    window_bytes = 8 * nch * nch * (len(order) + (lags if full else 0))
-    expect = window_count(pro.shape[layout.axis], W, step)
-    need = window_bytes * expect
-    torch = dev.torch
-    xparts, parts, host = [], [], None
-    for x, n, host in _stream._launches(who, pro, W, step, kind, layout.to2d, window_bytes):
-        if not xparts and not parts and not host and need > torch.cuda.mem_get_info()[0]:   # (before the first launch)
-            raise MemoryError(f"window_xcorr: the results of {expect} windows, {len(order)} x ({nch}, {nch}) float64 "
-                              f"each{f' and {lags} more for xcorr' if full else ''}, need {need / 1e9:.2f} GB, more "
-                              f"than the {torch.cuda.mem_get_info()[0] / 1e9:.2f} GB of device memory that are free: "
-                              f"raise step (now {step}; winsize {W}), lower maxlag (now {L}) or select fewer of "
-                              f"the {nch} channels")
-        xc = torch.empty((n, lags, nch, nch), dtype=torch.float64, device=x.device) if full else None
-        out = torch.empty((len(order), n, nch, nch), dtype=torch.float64, device=x.device) if order else None
-        dev.window_xcorr(x, W, step, L, normalize, mask, xc, out)
-        if full:
-            xparts.append(xc.cpu().numpy() if host else xc)
-        if order:
-            parts.append(out.cpu().numpy() if host else out)
-    result = {}
-    if full:
-        result["xcorr"] = np.concatenate(xparts, axis=0) if host else torch.cat(xparts, dim=0)
-    if order:
-        planes = np.concatenate(parts, axis=1) if host else torch.cat(parts, dim=1)
-        for p, name in enumerate(order):
-            result[name] = planes[p]
-    out = {name: result[name] for name in names}
-    return out[names[0]].shape[0], out[names[0]] if _stream._is_one(measures) else out
+    planes, full = _stream._pair_planes(who, pro, W, step, kind, layout, layout.to2d, len(order),
+                                        lambda x, out, xc: dev.window_xcorr(x, W, step, L, normalize, mask, xc, out),
+                                        advice=f", lower maxlag (now {L})", lags=2 * L + 1 if "xcorr" in names else 0)
+    found = {name: planes[p] for p, name in enumerate(order)}
+    if full is not None:
+        found["xcorr"] = full
+    return found[names[0]].shape[0], _stream._asked(measures, names, found)

@@ -342,5 +342,5 @@ def test_xcorr_kernels_fit_their_budgets(tmp_path):
         if "xcorr_gram_kernel" in name:
             assert int(use["LDS Size"]) <= 80 * 1024
     # the window dimension of the grid: a batch is at most 65535 windows
-    source = open(os.path.join(csrc, "windowxcorr.hip")).read()
+    source = open(os.path.join(csrc, "pair_window.h")).read()
     assert re.search(r"batch > 65535 \? 65535", source)
