@@ -1256,6 +1256,57 @@ int64_t osz_window_granger_work(int nch, int64_t n, int64_t winsize, int64_t ste
 int osz_window_granger(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int order,
                        int mask, double *out, int64_t plane_pitch, double *work, int64_t work_len, void *stream);
 
+/* ---- binned mutual information per window and pair (features/mutual_info.py window_mutual_info) */
+/* (csrc/windowmi.hip, K25) */
+#define OSZ_WM_LONGEST 4096       /* the longest window: an int32 count is exact, phi(0 .. W) is a table      */
+#define OSZ_WM_MAXBINS 16         /* the most bins: the one-hot rows of a channel fill one matrix tile        */
+typedef enum {
+    OSZ_WM_COUNTS = 0,            /* n_ab(i, j): the joint histogram itself                                   */
+    OSZ_WM_MI = 1,                /* H_i + H_j - H_ij, nats                                                   */
+    OSZ_WM_NMI = 2,               /* MI / sqrt(H_i H_j) clipped to [0, 1]                                     */
+    OSZ_WM_JOINT = 3,             /* H_ij                                                                     */
+    OSZ_WM_COUNT = 4
+} osz_window_mi_measure;
+typedef enum {
+    OSZ_WM_QUANTILE = 0,          /* edges at the k / bins quantiles of the window (Hyndman & Fan type 7)     */
+    OSZ_WM_UNIFORM = 1            /* edges lo + k ((hi - lo) / bins), lo and hi the window's extremes         */
+} osz_window_mi_binning;
+/*
+ * The float64 work space of one osz_window_mi call with these arguments, in doubles: the table
+ * phi(0 .. winsize), and for a batch of windows the edges, marginal counts and bin codes per
+ * (channel, window) and the int32 joint counts, (nch Bp)^2 a window with Bp = bins rounded up to a
+ * power of two (at most 2^25 doubles, or one window's).  -1 for nch < 2 or > 16384, n < 0, winsize
+ * < 16 or > OSZ_WM_LONGEST, step < 1, bins < 2 or > OSZ_WM_MAXBINS, or an empty or unknown mask.
+ * Touches no device.
+ */
+int64_t osz_window_mi_work(int nch, int64_t n, int64_t winsize, int64_t step, int bins, int mask);
+/*
+ * x and the windows are those of osz_window_xcorr.  With W = winsize and B = bins, a window of a row
+ * has the edges e_1 <= .. <= e_{B-1}: the k / B quantiles of its samples, osz_window_quantiles'
+ * arithmetic to the bit (binning OSZ_WM_QUANTILE), or lo + k ((hi - lo) / B), each operation one
+ * IEEE operation (OSZ_WM_UNIFORM).  A sample's bin is the number of edges <= it; n_ab(i, j) counts
+ * the samples t with row i in bin a and row j in bin b; n_a(i) are the marginal counts.  With
+ * phi(n) = n ln n, phi(0) = 0, and S(.) the sum of phi over the cells in the order a, then b:
+ *   H_i = (phi(W) - S(n_a)) / W,  H_ij = (phi(W) - S(n_ab)) / W,  MI_ij = (H_i + H_j) - H_ij.
+ * For the nwin = osz_window_count(n, winsize, step) windows, with COUNTS in mask
+ *   counts[(((k * B + a) * B + b) * nch + i) * nch + j] = n_ab(i, j)                       (f64)
+ * and for every other measure m of mask (an osz_window_mi_measure), in the order of the enum,
+ *   out[p * plane_pitch + (k * nch + i) * nch + j] = measure of rows i and j over window k  (f64)
+ * with p the measure's rank among those present, COUNTS not counted.  counts is read only with
+ * COUNTS in mask, out only with another measure.  MI below 0 is written as +0.0; NMI is NaN where
+ * H_i H_j = 0.  Every measure is computed for i < j and written to both mirrors, counts[a, b, i, j]
+ * and counts[b, a, j, i] from one value.  The diagonal: MI = JOINT = H_i, NMI = 1.0 (NaN for H_i =
+ * 0), counts n_a for a = b and 0 elsewhere.  A row with a NaN or +-inf sample (under UNIFORM also
+ * one whose hi - lo is not finite) is NaN in its row and column in every measure, counts included.
+ * An entry's bits depend on winsize, bins, binning and the window's samples of rows i and j only:
+ * the counts are the int8 MFMA's exact int32 sums, phi is read from one table, the sums of phi run
+ * in an order that is a function of B alone, nothing is atomic.
+ * work: work_len >= osz_window_mi_work(...) doubles on the device, the caller's.
+ */
+int osz_window_mi(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int bins,
+                  int binning, int mask, double *counts, double *out, int64_t plane_pitch, double *work,
+                  int64_t work_len, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

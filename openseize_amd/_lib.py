@@ -87,6 +87,11 @@ WX_MAXLAG = 64       # OSZ_WX_MAXLAG: the largest maxlag (the halo of the rows s
 WINDOW_GRANGER = {"granger": 0, "instant": 1, "total": 2}
 WG_LONGEST = 4096    # OSZ_WG_LONGEST: the longest window of osz_window_granger
 WG_MAXORDER = 16     # OSZ_WG_MAXORDER: the largest model order (a pair's coefficient blocks are held in LDS)
+# OSZ_WM_*: a measure's bit in the mask of osz_window_mi is 1 << its value
+WINDOW_MI = {"counts": 0, "mi": 1, "nmi": 2, "joint": 3}
+MI_BINNING = {"quantile": 0, "uniform": 1}    # osz_window_mi_binning
+WM_LONGEST = 4096    # OSZ_WM_LONGEST: the longest window of osz_window_mi
+WM_MAXBINS = 16      # OSZ_WM_MAXBINS: the most bins (a channel's one-hot rows fill one matrix tile)
 # OSZ_SOSK_*: the kernel of a record of osz_sos_last_launches, and the record's fields in order
 SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_dual", "sos_dual_lean",
               "sos_dual2", "seal")
@@ -299,6 +304,9 @@ SIGNATURES = {
     "osz_window_granger_work": (c_i64, [ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int]),
     "osz_window_granger": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
                                           c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "osz_window_mi_work": (c_i64, [ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int]),
+    "osz_window_mi": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

@@ -1,5 +1,5 @@
 // pair_window.h -- what the channel-pair window kernels share: K19 windowpair.hip, K23
-// windowxcorr.hip and K24 windowgranger.hip.  DESIGN.md section 4.
+// windowxcorr.hip, K24 windowgranger.hip and K25 windowmi.hip.  DESIGN.md section 4.
 //
 // Host side: PwPlan and pw_plan, the work space of one push and the windows of a batch; pw_head,
 // the checks every entry point makes of its arguments; pw_batches, the walk over the batches; and
@@ -110,6 +110,12 @@ int wx_window_sums(const double *x, int64_t pitch, int nch, int64_t W, int64_t s
                    double *chan, const char *timer, hipStream_t st);
 int wx_lagged_gram(const double *x, int64_t pitch, int nch, int64_t W, int64_t step, int L, int64_t w0,
                    int64_t count, const double *chan, double *part, const char *timer, hipStream_t st);
+
+// K17's launcher (windowquant.hip), which K25 takes its quantile edges from: osz_window_quantiles
+// with its arguments and checks, on stream st, timed under the caller's label.
+int wq_quantiles(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
+                 const double *q, int nq, double *out, int64_t plane_pitch, int64_t row_pitch, int64_t win0,
+                 const char *label, hipStream_t st);
 
 typedef double pair_d4 __attribute__((ext_vector_type(4)));   // one lane's share of a 16 x 16 MFMA tile
 constexpr int kPwTile = 16;                                   // rows per side of an MFMA tile

@@ -238,15 +238,11 @@ static void wq_launch(const WqArgs &A, unsigned nblk, hipStream_t st) {
     hipLaunchKernelGGL((window_quantiles_kernel<NT, K>), dim3(nblk), dim3(NT), 0, st, A);
 }
 
-}  // namespace osz
-
-using namespace osz;
-
-extern "C" {
-
-int osz_window_quantiles(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
-                         const double *q, int nq, double *out, int64_t plane_pitch, int64_t row_pitch, int64_t win0,
-                         void *stream) {
+// osz_window_quantiles on a stream, timed under the caller's label (pair_window.h: K25 takes its bin
+// edges from here)
+int wq_quantiles(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
+                 const double *q, int nq, double *out, int64_t plane_pitch, int64_t row_pitch, int64_t win0,
+                 const char *label, hipStream_t st) {
     static const WinRule rule = {"osz_window_quantiles", "measure", OSZ_WQ_COUNT, 4, OSZ_WQ_LONGEST};
     const int planes = __builtin_popcount(mask & 3) + ((mask >> OSZ_WQ_QUANTILE) & 1) * nq;
     WqArgs A;
@@ -271,8 +267,7 @@ int osz_window_quantiles(const double *x, int64_t pitch, int nch, int64_t n, int
     if (int rc = win_grid(rule, A, nch, nblk)) return rc;
     int wpad = OSZ_WQ_NARROWEST;
     while (wpad < winsize) wpad <<= 1;
-    hipStream_t st = as_stream(stream);
-    KernelTimer timer("window_quantiles", st);
+    KernelTimer timer(label, st);
     switch (wpad) {                                        // up to OSZ_WQ_WAVE one wave, 256 threads above
     case 64: wq_launch<64, 1>(A, nblk, st); break;
     case 128: wq_launch<64, 2>(A, nblk, st); break;
@@ -284,6 +279,19 @@ int osz_window_quantiles(const double *x, int64_t pitch, int nch, int64_t n, int
     }
     OSZ_HIP(hipGetLastError());
     return OSZ_OK;
+}
+
+}  // namespace osz
+
+using namespace osz;
+
+extern "C" {
+
+int osz_window_quantiles(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
+                         const double *q, int nq, double *out, int64_t plane_pitch, int64_t row_pitch, int64_t win0,
+                         void *stream) {
+    return wq_quantiles(x, pitch, nch, n, winsize, step, mask, q, nq, out, plane_pitch, row_pitch, win0,
+                        "window_quantiles", as_stream(stream));
 }
 
 }  // extern "C"

@@ -162,11 +162,11 @@ def _planes(who, pro, W, step, kind, layout, count, launch):
     return parts, host
 
 
-def _pair_planes(who, pro, W, step, kind, layout, rows, count, launch, advice="", lags=0):
+def _pair_planes(who, pro, W, step, kind, layout, rows, count, launch, advice="", lags=0, more_for="xcorr"):
     """The launches of a channel-pair function that writes ``count`` (nch, nch) planes per window and,
-    with ``lags`` (window_xcorr's ``"xcorr"``), ``lags`` more in an array of their own: for every
-    ``(x, n, host)`` of ``_launches``, ``launch(x, out, more)`` fills ``out``, a float64 (count, n, nch,
-    nch) CUDA tensor allocated here (None for no plane), and ``more``, (n, lags, nch, nch) (None for
+    with ``lags`` (window_xcorr's ``"xcorr"``; ``more_for`` is the noun a message gives them), ``lags``
+    more in an array of their own: for every ``(x, n, host)`` of ``_launches``, ``launch(x, out,
+    more)`` fills ``out``, a float64 (count, n, nch, nch) CUDA tensor allocated here (None for no plane), and ``more``, (n, lags, nch, nch) (None for
     no lag); both go down to the host if ``host``.  Returns ``(planes, more)`` of the whole stream,
     (count, nwin, nch, nch) and (nwin, lags, nch, nch).  CUDA-fed results stay on the device: when
     they exceed the free device memory, MemoryError before the first launch, with ``advice`` on
@@ -181,7 +181,7 @@ def _pair_planes(who, pro, W, step, kind, layout, rows, count, launch, advice=""
             need, free = window_bytes * expect, torch.cuda.mem_get_info()[0]
             if need > free:
                 raise MemoryError(f"{who}: the results of {expect} windows, {count} x ({nch}, {nch}) float64 each"
-                                  f"{f' and {lags} more for xcorr' if lags else ''}, need {need / 1e9:.2f} GB, more than "
+                                  f"{f' and {lags} more for {more_for}' if lags else ''}, need {need / 1e9:.2f} GB, more than "
                                   f"the {free / 1e9:.2f} GB of device memory that are free: raise step (now {step}; "
                                   f"winsize {W}){advice} or select fewer of the {nch} channels")
         out = empty((count, n, nch, nch), device=x.device) if count else None
