@@ -1307,6 +1307,56 @@ int osz_window_mi(const double *x, int64_t pitch, int nch, int64_t n, int64_t wi
                   int binning, int mask, double *counts, double *out, int64_t plane_pitch, double *work,
                   int64_t work_len, void *stream);
 
+/* ---- binned transfer entropy per window and ordered pair (features/transfer_entropy.py) */
+/* (csrc/windowte.hip, K26) */
+#define OSZ_WT_LONGEST 4096       /* the longest window, osz_window_mi's                                      */
+#define OSZ_WT_MAXBINS 8          /* the most bins: a (bin now, bin before) symbol is one byte below 0xFF     */
+#define OSZ_WT_MAXLAG 64          /* the largest lag of the source                                            */
+typedef enum {
+    OSZ_WT_COUNTS = 0,            /* n_abc(i, j): the three-way histogram itself                              */
+    OSZ_WT_TE = 1,                /* I(Y_t ; X_{t-u} | Y_{t-1}), nats, source i (row) to target j (column)    */
+    OSZ_WT_NTE = 2,               /* TE / H(Y_t | Y_{t-1}) clipped to [0, 1]                                  */
+    OSZ_WT_NET = 3,               /* TE[i, j] - TE[j, i]                                                      */
+    OSZ_WT_COUNT = 4
+} osz_window_te_measure;
+/*
+ * The float64 work space of one osz_window_te call with these arguments, in doubles: the table
+ * phi(0 .. winsize), and for a batch of windows osz_window_mi's edges, marginal counts and bin
+ * codes per (channel, window), as many bytes of symbols again and the int32 counts, (nch Bp^2) x
+ * (nch Bp) a window with Bp = bins rounded up to a power of two (at most 2^25 doubles, or one
+ * window's).  -1 for nch < 2 or > 16384, n < 0, winsize < 16 or > OSZ_WT_LONGEST, step < 1, bins
+ * < 2 or > OSZ_WT_MAXBINS, lag < 1 or > min(OSZ_WT_MAXLAG, winsize / 2), or an empty or unknown
+ * mask.  Touches no device.
+ */
+int64_t osz_window_te_work(int nch, int64_t n, int64_t winsize, int64_t step, int bins, int lag, int mask);
+/*
+ * x, the windows, the edges and the bins (binning: an osz_window_mi_binning) are those of
+ * osz_window_mi: the bins of a window are cut from all W = winsize samples.  With B = bins, u = lag
+ * and T = W - u, n_abc(i, j) counts the t = u .. W - 1 of the window with the target, row j, in bin
+ * a at t and in bin b at t - 1 and the source, row i, in bin c at t - u.  With phi(n) = n ln n,
+ * phi(0) = 0, every sum in one thread, b outermost, then a, then c:
+ *   S3 = sum_bac phi(n_abc)          Sab = sum_ba phi(sum_c n_abc)
+ *   Sbc = sum_bc phi(sum_a n_abc)    Sb = sum_b phi(sum_ac n_abc)     (the inner sums are integers)
+ *   TE = ((S3 - Sab) - (Sbc - Sb)) / T,   Hc = (Sb - Sab) / T.
+ * For the nwin = osz_window_count(n, winsize, step) windows, with COUNTS in mask
+ *   counts[((((k * B + a) * B + b) * B + c) * nch + i) * nch + j] = n_abc(i, j)            (f64)
+ * and for every other measure m of mask (an osz_window_te_measure), in the order of the enum,
+ *   out[p * plane_pitch + (k * nch + i) * nch + j] = measure from row i to row j, window k  (f64)
+ * with p the measure's rank among those present, COUNTS not counted.  counts is read only with
+ * COUNTS in mask, out only with another measure.  A finite TE below 0 is written as +0.0; NTE is
+ * TE / Hc clipped to [0, 1], NaN where Hc = 0; NET[i, j] is TE[i, j] - TE[j, i] and NET[j, i] is
+ * TE[j, i] - TE[i, j], each one subtraction.  The diagonal of TE, NTE and NET is +0.0; counts[..,
+ * i, i] is what the definition gives.  A row with a NaN or +-inf sample (under UNIFORM also one
+ * whose hi - lo is not finite) is NaN in its row and column in every measure, counts included.
+ * An entry's bits depend on winsize, bins, lag, binning and the window's samples of rows i and j
+ * only: the counts are the int8 MFMA's exact int32 sums, phi is read from one table, the sums of
+ * phi run in an order that is a function of B alone, nothing is atomic.
+ * work: work_len >= osz_window_te_work(...) doubles on the device, the caller's.
+ */
+int osz_window_te(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int bins,
+                  int lag, int binning, int mask, double *counts, double *out, int64_t plane_pitch, double *work,
+                  int64_t work_len, void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

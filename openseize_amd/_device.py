@@ -1481,7 +1481,7 @@ def bispec_finish(mode, count, k_lo, sums, power):
 def name_mask(table, names):
     """The bit mask a kernel takes for ``names``, keys of ``table``: one of _lib.WINDOW_FEATURE,
     WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL, WINDOW_CONNECTIVITY, WINDOW_FRACTAL, WINDOW_WAVELET,
-    WINDOW_AR, WINDOW_XCORR, WINDOW_GRANGER and WINDOW_MI, name -> bit."""
+    WINDOW_AR, WINDOW_XCORR, WINDOW_GRANGER, WINDOW_MI and WINDOW_TE, name -> bit."""
     mask = 0
     for name in names:
         mask |= 1 << table[name]
@@ -1781,4 +1781,38 @@ def window_mi(x2d, winsize, step, bins, binning, mask, counts, out):
         _lib.check(lib.osz_window_mi(ptr(x2d), pitch, nch, n, int(winsize), int(step), int(bins), int(binning),
                                      int(mask), ptr(counts) if mask & 1 else None, ptr(out) if planes else None,
                                      out.stride(0) if planes else 0, ptr(work), work.numel(), stream_ptr()))
+    return nwin
+
+
+def window_te_work(nch, n, winsize, step, bins, lag, mask):
+    """osz_window_te_work: the doubles of work space a ``window_te`` call over (nch, n) rows asks for,
+    -1 for sizes the library refuses.  Touches no device."""
+    return _lib.load().osz_window_te_work(int(nch), int(n), int(winsize), int(step), int(bins), int(lag), int(mask))
+
+
+def window_te(x2d, winsize, step, bins, lag, binning, mask, counts, out):
+    """osz_window_te: the measures in the bit mask ``mask`` (_lib.WINDOW_TE) of every window of
+    ``winsize`` samples, ``step`` apart, that x2d -- (nch, n) float64 CUDA rows, unit stride along n --
+    holds, from ``bins`` bins per row cut by ``binning`` (a value of _lib.MI_BINNING) with the source
+    ``lag`` samples back.  ``counts``: a contiguous float64 (nwin, bins ** 3, nch, nch) CUDA tensor,
+    written as counts[k, (a * bins + b) * bins + c, i, j] with the counts bit set, else None.  ``out``:
+    a contiguous float64 (planes, nwin, nch, nch) CUDA tensor, one plane per measure of te, nte and net
+    present, in that order (row the source, column the target), else None.  The work space is
+    allocated here and freed on return.  Returns the number of windows written."""
+    lib, nch, n, nwin, pitch, work = _pair_open("window_te", x2d, winsize, step, mask, (int(bins), int(lag), int(mask)),
+                                                binning in (0, 1), f"{bins}, {lag}, {binning!r}", None, None)
+    cells = int(bins) ** 3
+    planes = bin(int(mask) >> 1).count("1")
+    want = ((counts, (nwin, cells, nch, nch), mask & 1), (out, (planes, nwin, nch, nch), planes))
+    for arr, shape, asked in want:
+        if (arr is None) != (not asked) or (asked and (arr.dtype != torch.float64 or tuple(arr.shape) != shape
+                                                       or not arr.is_contiguous() or arr.device != x2d.device)):
+            raise ValueError(f"window_te: mask {mask} takes counts and out contiguous float64 "
+                             f"{[s if a else None for _, s, a in want]}, got "
+                             f"{[None if a is None else tuple(a.shape) for a, _, _ in want]}")
+    if nwin:
+        _lib.check(lib.osz_window_te(ptr(x2d), pitch, nch, n, int(winsize), int(step), int(bins), int(lag),
+                                     int(binning), int(mask), ptr(counts) if mask & 1 else None,
+                                     ptr(out) if planes else None, out.stride(0) if planes else 0, ptr(work),
+                                     work.numel(), stream_ptr()))
     return nwin

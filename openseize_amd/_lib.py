@@ -92,6 +92,11 @@ WINDOW_MI = {"counts": 0, "mi": 1, "nmi": 2, "joint": 3}
 MI_BINNING = {"quantile": 0, "uniform": 1}    # osz_window_mi_binning
 WM_LONGEST = 4096    # OSZ_WM_LONGEST: the longest window of osz_window_mi
 WM_MAXBINS = 16      # OSZ_WM_MAXBINS: the most bins (a channel's one-hot rows fill one matrix tile)
+# OSZ_WT_*: a measure's bit in the mask of osz_window_te is 1 << its value; the binnings are MI_BINNING
+WINDOW_TE = {"counts": 0, "te": 1, "nte": 2, "net": 3}
+WT_LONGEST = 4096    # OSZ_WT_LONGEST: the longest window of osz_window_te
+WT_MAXBINS = 8       # OSZ_WT_MAXBINS: the most bins (a (bin now, bin before) symbol is one byte below 0xFF)
+WT_MAXLAG = 64       # OSZ_WT_MAXLAG: the largest lag of the source
 # OSZ_SOSK_*: the kernel of a record of osz_sos_last_launches, and the record's fields in order
 SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_dual", "sos_dual_lean",
               "sos_dual2", "seal")
@@ -307,6 +312,9 @@ SIGNATURES = {
     "osz_window_mi_work": (c_i64, [ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int]),
     "osz_window_mi": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "osz_window_te_work": (c_i64, [ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "osz_window_te": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

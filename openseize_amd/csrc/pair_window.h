@@ -1,9 +1,10 @@
 // pair_window.h -- what the channel-pair window kernels share: K19 windowpair.hip, K23
-// windowxcorr.hip, K24 windowgranger.hip and K25 windowmi.hip.  DESIGN.md section 4.
+// windowxcorr.hip, K24 windowgranger.hip, K25 windowmi.hip and K26 windowte.hip.  DESIGN.md section 4.
 //
 // Host side: PwPlan and pw_plan, the work space of one push and the windows of a batch; pw_head,
 // the checks every entry point makes of its arguments; pw_batches, the walk over the batches; and
-// wx_window_sums and wx_lagged_gram, K23's sums and Gram launches, which K24 starts from too.  An
+// wx_window_sums and wx_lagged_gram, K23's sums and Gram launches, which K24 starts from too, and
+// wm_phi and wm_codes, K25's table and bin codes, which K26 starts from too.  An
 // entry point keeps the conditions of its own parameters and its launches.  Device side: the sums
 // kernel and the LDS turn that writes a mirror.  The Gram kernels keep their staging and MFMA
 // loops, 64 against 32 rows a side, sub-blocks against groups of lags, and with them their tile
@@ -116,6 +117,25 @@ int wx_lagged_gram(const double *x, int64_t pitch, int nch, int64_t W, int64_t s
 int wq_quantiles(const double *x, int64_t pitch, int nch, int64_t n, int64_t winsize, int64_t step, int mask,
                  const double *q, int nq, double *out, int64_t plane_pitch, int64_t row_pitch, int64_t win0,
                  const char *label, hipStream_t st);
+
+// K25's phi table, edges and bin codes (windowmi.hip), which K26 starts from too, each launch timed
+// under the caller's label.  wm_phi: phi[n] = n ln n for n = 0 .. W.  wm_codes, for x (nch rows of
+// pitch `pitch`) at the first of `count` <= 65535 windows of W samples, `step` apart: the edges of
+// the `bins` bins (binning OSZ_WM_QUANTILE: through wq_quantiles into `edges`, OSZ_WM_MAXBINS
+// doubles per (row, window); OSZ_WM_UNIFORM: inside the code kernel), then per (window w, row c)
+// the codes, codes[(w * nch + c) * wpad + t] = the bin of sample t, 0xFF for W <= t < wpad (wpad: W
+// rounded up to a multiple of 64), and meta[(w * nch + c) * (OSZ_WM_MAXBINS + 2) + ..]: the
+// marginal counts, at OSZ_WM_MAXBINS their sum of phi, at OSZ_WM_MAXBINS + 1 the non-finite flag.
+int wm_phi(double *phi, int W, const char *label, hipStream_t st);
+int wm_codes(const double *x, int64_t pitch, int nch, int W, int64_t step, int64_t count, int bins, int binning,
+             const double *phi, double *edges, double *meta, unsigned char *codes, int wpad, const char *edges_label,
+             const char *code_label, hipStream_t st);
+
+// where the bytes of the word w equal those of `same` (a byte repeated four times): 1, else 0
+__device__ __forceinline__ unsigned mi_onehot(unsigned w, unsigned same) {
+    const unsigned x = w ^ same, low = 0x7F7F7F7Fu;
+    return (~(((x & low) + low) | x | low)) >> 7;
+}
 
 typedef double pair_d4 __attribute__((ext_vector_type(4)));   // one lane's share of a 16 x 16 MFMA tile
 constexpr int kPwTile = 16;                                   // rows per side of an MFMA tile

@@ -14,6 +14,8 @@
 //     workgroup, not once per operand register -- and writes the block-upper triangle of N;
 // (4) mi_finish_kernel sums phi(n_ab) by table lookup per pair i < j, forms the measures and
 //     writes both mirrors.  phi(0 .. W) is computed once per call (mi_phi_kernel).
+// Steps (1) and (2) and the table are also host launchers, wm_codes and wm_phi (pair_window.h): K26
+// (windowte.hip) starts from the same bytes.
 // DESIGN.md section 4, K25.
 //
 // The counts are integers; phi is read from one table, so it is a function of n alone; a sum of
@@ -147,12 +149,6 @@ __global__ void __launch_bounds__(NT) mi_code_kernel(const MiCode A) {
         meta[kMiSphi] = s;
         meta[kMiFlag] = wilds ? 1.0 : 0.0;
     }
-}
-
-// where the bytes of the word w equal those of `same` (a byte repeated four times): 1, else 0
-__device__ __forceinline__ unsigned mi_onehot(unsigned w, unsigned same) {
-    const unsigned x = w ^ same, low = 0x7F7F7F7Fu;
-    return (~(((x & low) + low) | x | low)) >> 7;
 }
 
 // N of one window over one 64 x 64 block of one-hot rows (block row bi <= block column bj).  Row r
@@ -374,6 +370,33 @@ static void wm_code(const MiCode &A, hipStream_t st) {
     hipLaunchKernelGGL((mi_code_kernel<NT, K>), dim3((unsigned)A.count, (unsigned)A.nch), dim3(NT), 0, st, A);
 }
 
+int wm_phi(double *phi, int W, const char *label, hipStream_t st) {
+    KernelTimer timer(label, st);
+    hipLaunchKernelGGL(mi_phi_kernel, dim3((unsigned)(W / 256 + 1)), dim3(256), 0, st, phi, W);
+    OSZ_HIP(hipGetLastError());
+    return OSZ_OK;
+}
+
+int wm_codes(const double *x, int64_t pitch, int nch, int W, int64_t step, int64_t count, int bins, int binning,
+             const double *phi, double *edges, double *meta, unsigned char *codes, int wpad, const char *edges_label,
+             const char *code_label, hipStream_t st) {
+    if (binning == OSZ_WM_QUANTILE) {
+        double q[OSZ_WQ_QMOST];
+        for (int k = 1; k < bins; ++k) q[k - 1] = (double)k / (double)bins;
+        const int rc = wq_quantiles(x, pitch, nch, (count - 1) * step + W, W, step, 1 << OSZ_WQ_QUANTILE, q, bins - 1, edges,
+                                    nch * count, count, 0, edges_label, st);
+        if (rc != OSZ_OK) return rc;
+    }
+    const MiCode C{x, pitch, step, count, nch, W, wpad, bins, binning == OSZ_WM_UNIFORM, phi, edges, meta, codes};
+    KernelTimer timer(code_label, st);
+    if (W <= 64) wm_code<64, 1>(C, st);
+    else if (W <= 256) wm_code<64, 4>(C, st);
+    else if (W <= 1024) wm_code<256, 4>(C, st);
+    else wm_code<1024, 4>(C, st);
+    OSZ_HIP(hipGetLastError());
+    return OSZ_OK;
+}
+
 template <int LB>
 static void wm_finish(unsigned tri, unsigned count, size_t lds, hipStream_t st, const int *part, const double *meta,
                       const double *table, int nch, int ntile, int B, int W, int mask, double *counts, double *out,
@@ -408,32 +431,14 @@ int osz_window_mi(const double *x, int64_t pitch, int nch, int64_t n, int64_t wi
     double *phi = work, *edges = phi + p.phi, *meta = edges + p.edges;
     unsigned char *codes = reinterpret_cast<unsigned char *>(meta + p.meta);
     int *part = reinterpret_cast<int *>(work + p.chan);
-    double q[OSZ_WQ_QMOST];
-    for (int k = 1; k < bins; ++k) q[k - 1] = (double)k / (double)bins;
     const int rows = nch << p.lb;
     const int nblk = (rows + kMiSide - 1) / kMiSide, ntile = (nch + kMiFinish - 1) / kMiFinish;
-    {
-        KernelTimer timer("window_mi_phi", st);
-        hipLaunchKernelGGL(mi_phi_kernel, dim3((unsigned)(W / 256 + 1)), dim3(256), 0, st, phi, W);
-        OSZ_HIP(hipGetLastError());
-    }
+    const int rc_phi = wm_phi(phi, W, "window_mi_phi", st);
+    if (rc_phi != OSZ_OK) return rc_phi;
     return pw_batches(p, [&](int64_t w0, int64_t count) -> int {
-        const double *x0 = x + w0 * step;
-        if (binning == OSZ_WM_QUANTILE) {
-            const int rc = wq_quantiles(x0, pitch, nch, (count - 1) * step + winsize, winsize, step, 1 << OSZ_WQ_QUANTILE, q,
-                                        bins - 1, edges, nch * count, count, 0, "window_mi_edges", st);
-            if (rc != OSZ_OK) return rc;
-        }
-        {
-            const MiCode C{x0, pitch, step, count, nch, W, (int)p.wpad, bins, binning == OSZ_WM_UNIFORM, phi, edges, meta,
-                           codes};
-            KernelTimer timer("window_mi_code", st);
-            if (W <= 64) wm_code<64, 1>(C, st);
-            else if (W <= 256) wm_code<64, 4>(C, st);
-            else if (W <= 1024) wm_code<256, 4>(C, st);
-            else wm_code<1024, 4>(C, st);
-            OSZ_HIP(hipGetLastError());
-        }
+        const int rc = wm_codes(x + w0 * step, pitch, nch, W, step, count, bins, binning, phi, edges, meta, codes,
+                                (int)p.wpad, "window_mi_edges", "window_mi_code", st);
+        if (rc != OSZ_OK) return rc;
         {
             KernelTimer timer("window_mi_gram", st);
             hipLaunchKernelGGL(mi_gram_kernel, dim3((unsigned)(nblk * (nblk + 1) / 2), (unsigned)count), dim3(kMiThreads), 0,
