@@ -1357,6 +1357,48 @@ int osz_window_te(const double *x, int64_t pitch, int nch, int64_t n, int64_t wi
                   int lag, int binning, int mask, double *counts, double *out, int64_t plane_pitch, double *work,
                   int64_t work_len, void *stream);
 
+/* ---- banded spectral connectivity per window (features/coherence.py) */
+/* (csrc/windowcoh.hip, K27) */
+#define OSZ_WK_BANDS_MOST 16      /* the most bands of one call                                               */
+typedef enum {
+    OSZ_WK_COH = 0,               /* |sum z|^2 / (sum |X_i|^2 sum |X_j|^2), z = conj(X_i) X_j                 */
+    OSZ_WK_IMCOH = 1,             /* Im sum z / sqrt(sum |X_i|^2 sum |X_j|^2)                                 */
+    OSZ_WK_PLV = 2,               /* |sum z / |z|| / N                                                        */
+    OSZ_WK_PLI = 3,               /* |sum sign d| / N, d = Im z                                               */
+    OSZ_WK_WPLI = 4,              /* |sum d| / sum |d|                                                        */
+    OSZ_WK_DWPLI = 5,             /* ((sum d)^2 - sum d^2) / ((sum |d|)^2 - sum d^2)                          */
+    OSZ_WK_COUNT = 6
+} osz_window_coherence_measure;
+/*
+ * The float64 work space of one osz_window_coherence call with these arguments, in doubles: 0, the
+ * sums of a window stay in registers and its bins are folded in LDS.  -1 for nseg < 0 or >= 2^31,
+ * nch < 2 or > 16384, nfreq < 2, nch * nfreq >= 2^27, nsub < 2, mstep < 1, nbands < 1 or >
+ * OSZ_WK_BANDS_MOST, or an empty or unknown mask.  Touches no device.
+ */
+int64_t osz_window_coherence_work(int64_t nseg, int nch, int nfreq, int nsub, int mstep, int nbands, int mask);
+/*
+ * X: the contiguous complex128 (nseg, nch, nfreq) segment spectra of an OSZ_SPEC_DFT_SEGMENTS
+ * push, on the device.  Window k is the N = nsub segments k * mstep .. k * mstep + nsub - 1, nwin =
+ * (nseg - nsub) / mstep + 1 of them (0 for nseg < nsub: osz_window_count's rule, from nsub = 2 on).  bands: nbands pairs [b0, b1) of bins on the host,
+ * 1 <= b0 < b1 <= nfreq (the caller keeps a real Nyquist bin out).  Per window, pair and bin the
+ * sums over the window's segments, in segment order, are osz_cross_accumulate's (of X for COH and
+ * IMCOH, of X / |X| for PLV) and osz_lag_accumulate's (PLI, WPLI, DWPLI), and the measure is the
+ * definition above with N = nsub; a band's value is the sum of its bins' values in bin order times
+ * 1 / (b1 - b0).  For every measure m of mask (bit 1 << m), in the order of the enum,
+ *   out[p * plane_pitch + (((k * nbands + b) * nch + i) * nch + j)] = measure of band b, window k (f64)
+ * with p the measure's rank among those present; plane_pitch >= nwin * nbands * nch * nch.  [j, i]
+ * is written from the value of [i, j], i < j (IMCOH: negated, a zero +0.0 on both sides).  The
+ * diagonal is 1.0 for COH and PLV and 0.0 for the others.  A channel whose own sums are NaN in a
+ * bin of the band -- a non-finite spectrum value; for COH, IMCOH and PLV also one without power --
+ * is NaN in its row and column, the diagonal included; a zero denominator gives the NaN it gives.
+ * An entry's bits depend on nsub, the band's bins and the window's spectra of channels i and j
+ * only; nothing is atomic.  Arguments that hold no window return OSZ_OK and launch nothing.
+ * work: work_len >= osz_window_coherence_work(...) doubles, the caller's; it may be null.
+ */
+int osz_window_coherence(const void *X, int64_t nseg, int nch, int nfreq, int nsub, int mstep, const int *bands,
+                         int nbands, int mask, double *out, int64_t plane_pitch, double *work, int64_t work_len,
+                         void *stream);
+
 /* ---- EDF record decode ----------------------------- */
 /*
  * Replaces the host-side unpacking of edf.Reader (reference

@@ -1481,7 +1481,7 @@ def bispec_finish(mode, count, k_lo, sums, power):
 def name_mask(table, names):
     """The bit mask a kernel takes for ``names``, keys of ``table``: one of _lib.WINDOW_FEATURE,
     WINDOW_ENTROPY, WINDOW_QUANTILE, WINDOW_SPECTRAL, WINDOW_CONNECTIVITY, WINDOW_FRACTAL, WINDOW_WAVELET,
-    WINDOW_AR, WINDOW_XCORR, WINDOW_GRANGER, WINDOW_MI and WINDOW_TE, name -> bit."""
+    WINDOW_AR, WINDOW_XCORR, WINDOW_GRANGER, WINDOW_MI, WINDOW_TE and WINDOW_COHERENCE, name -> bit."""
     mask = 0
     for name in names:
         mask |= 1 << table[name]
@@ -1815,4 +1815,37 @@ def window_te(x2d, winsize, step, bins, lag, binning, mask, counts, out):
                                      int(binning), int(mask), ptr(counts) if mask & 1 else None,
                                      ptr(out) if planes else None, out.stride(0) if planes else 0, ptr(work),
                                      work.numel(), stream_ptr()))
+    return nwin
+
+
+def window_coherence(X, nsub, mstep, bands, mask, out):
+    """osz_window_coherence: the measures in the bit mask ``mask`` (_lib.WINDOW_COHERENCE) of every
+    window of ``nsub`` consecutive segments, ``mstep`` apart, that X -- a contiguous complex128 (nseg,
+    nch, nfreq) CUDA tensor of segment spectra, what a SPEC_DFT_SEGMENTS push returns -- holds, as the
+    mean over the bins of every band of ``bands``: pairs of bins (b0, b1), b1 exclusive, 1 <= b0 < b1
+    <= nfreq.  Written to out[p, k, b, i, j]: out a contiguous float64 (planes, nwin, nbands, nch, nch)
+    CUDA tensor on the device of X, one plane per measure present in the order of
+    _lib.WINDOW_COHERENCE.  The kernel takes no work space.  Returns the number of windows written."""
+    lib = require_gpu()
+    if X.dtype != torch.complex128 or X.ndim != 3 or not X.is_contiguous() or not X.is_cuda:
+        raise ValueError(f"window_coherence: X {tuple(X.shape)} {X.dtype} is not a contiguous complex128 (nseg, nch, "
+                         "nfreq) CUDA tensor")
+    nseg, nch, nfreq = X.shape
+    pairs = [(int(a), int(b)) for a, b in bands]
+    need = lib.osz_window_coherence_work(nseg, nch, nfreq, int(nsub), int(mstep), len(pairs), int(mask))
+    if need < 0 or any(not 1 <= a < b <= nfreq for a, b in pairs):
+        raise ValueError(f"window_coherence: bad sizes, bands or measures ({nseg}, {nch}, {nfreq}, {nsub}, {mstep}, "
+                         f"{pairs}, {mask})")
+    nwin = 0 if nseg < nsub else (nseg - int(nsub)) // int(mstep) + 1
+    planes = bin(int(mask)).count("1")
+    if (out.dtype != torch.float64 or tuple(out.shape) != (planes, nwin, len(pairs), nch, nch) or not out.is_contiguous()
+            or out.device != X.device):
+        raise ValueError(f"window_coherence: out {tuple(out.shape)} is not contiguous float64 ({planes}, {nwin}, "
+                         f"{len(pairs)}, {nch}, {nch}) on the device of the spectra")
+    if nwin:
+        work = torch.empty(need, dtype=torch.float64, device=X.device) if need else None
+        barr = (ctypes.c_int * (2 * len(pairs)))(*[b for pair in pairs for b in pair])
+        _lib.check(lib.osz_window_coherence(ptr(X), nseg, nch, nfreq, int(nsub), int(mstep),
+                                            ctypes.cast(barr, ctypes.c_void_p), len(pairs), int(mask), ptr(out),
+                                            out.stride(0), ptr(work) if need else None, need, stream_ptr()))
     return nwin

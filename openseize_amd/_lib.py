@@ -97,6 +97,9 @@ WINDOW_TE = {"counts": 0, "te": 1, "nte": 2, "net": 3}
 WT_LONGEST = 4096    # OSZ_WT_LONGEST: the longest window of osz_window_te
 WT_MAXBINS = 8       # OSZ_WT_MAXBINS: the most bins (a (bin now, bin before) symbol is one byte below 0xFF)
 WT_MAXLAG = 64       # OSZ_WT_MAXLAG: the largest lag of the source
+# OSZ_WK_*: a measure's bit in the mask of osz_window_coherence is 1 << its value
+WINDOW_COHERENCE = {"coh": 0, "imcoh": 1, "plv": 2, "pli": 3, "wpli": 4, "dwpli": 5}
+WK_BANDS_MOST = 16   # OSZ_WK_BANDS_MOST: the most bands of one call
 # OSZ_SOSK_*: the kernel of a record of osz_sos_last_launches, and the record's fields in order
 SOS_KERNEL = ("sos_kernel", "sos_split", "sos_split_lean", "sos_split2", "sos_dual", "sos_dual_lean",
               "sos_dual2", "seal")
@@ -315,6 +318,10 @@ SIGNATURES = {
     "osz_window_te_work": (c_i64, [ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "osz_window_te": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "osz_window_coherence_work": (c_i64, [c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int]),
+    "osz_window_coherence": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp,
+                                            ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "osz_simpson": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_i64, ctypes.c_double,
                                    c_vp, c_vp]),
     "osz_host_copy2d": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64]),

@@ -11,3 +11,4 @@ from openseize_amd.features.xcorr import WINDOW_XCORR, window_xcorr, xcorr_lags 
 from openseize_amd.features.granger import WINDOW_GRANGER, window_granger  # noqa: F401
 from openseize_amd.features.mutual_info import MI_BINNINGS, WINDOW_MI, window_mutual_info  # noqa: F401
 from openseize_amd.features.transfer_entropy import WINDOW_TE, window_transfer_entropy  # noqa: F401
+from openseize_amd.features.coherence import WINDOW_COHERENCE, window_coherence  # noqa: F401
